@@ -11,9 +11,11 @@ patches, SparseImgAlign only.  `value` is that and nothing else.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: spawns one rank per GPU itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                            (the headline and every leg below)
+    python bench.py ... --dump-outputs DIR                (the last timed step's results as DIR/*.npy)
 
-Prints ONE JSON line on rank 0.  Extra keys of that line (N = 1 only, each leg is
-independent and never changes `value`):
+Prints ONE JSON line on rank 0.  A plain run measures the headline and nothing else.  Extra
+keys of that line with --full (N = 1 only, each leg is independent and never changes `value`):
   roofline / parity / cpu_baseline   the headline kernel (K1)
   align_plus_refine                  K1 + pose_optimizer (K4) timed together
   full_track                         BASELINE configs[2]: K1 + findMatchDirect + K4 + updateSeeds,
@@ -118,6 +120,8 @@ def roofline(kernel: str, alg_bytes: float, ms: float, **extra) -> dict:
     return d
 
 
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20240601           # ... the rows kept of outputs above that
 DETAILS_FILE = "bench_details.json"   # the full result object (every leg); the LAST stdout line is the compact summary
 COMPACT_LIMIT = 6000                  # bytes: the driver parses the tail of stdout (BENCH_r03: a 21 KB line was not parsed -- its record
                                       # holds the last 14 161 bytes of stdout; rounds 4-5 stayed below 4 000, this round's line carries the
@@ -277,6 +281,42 @@ def write_details(result: dict) -> str | None:
         except OSError:
             pass
     return where
+
+
+def dump_outputs(out_dir: str, results: dict) -> dict:
+    """--dump-outputs: every tensor of the result objects the timed path hands its caller, as out_dir/<prefix>_<field>.npy.
+    Floating tensors keep f64 or become f32; integer and flag tensors are written exactly (f32 up to 16 bits, else f64).
+    Above DUMP_LIMIT_BYTES in all, the largest arrays keep a sample of their rows, picked by a fixed seed (the indices go
+    to <name>_rows.npy), so that two runs with the same arguments write comparable files."""
+    import dataclasses
+    arrays = {}
+    for prefix, obj in results.items():
+        fields = {f.name: getattr(obj, f.name) for f in dataclasses.fields(obj)} if dataclasses.is_dataclass(obj) else {"": obj}
+        for k, t in fields.items():
+            if isinstance(t, torch.Tensor):
+                a = t.detach().cpu().numpy()
+                if a.dtype != np.float64:
+                    a = a.astype(np.float32 if a.dtype.kind == "f" or a.dtype.itemsize <= 2 else np.float64)
+                arrays[f"{prefix}_{k}" if k else prefix] = a
+    # water-filling: the smallest arrays are written whole; the ones that do not fit share what is left equally, as a sample
+    # of their rows (each kept row costs its bytes and its 8-byte index; 64 KB are kept back for the .npy headers)
+    left, keep = DUMP_LIMIT_BYTES - (1 << 16), {}
+    order = sorted(arrays, key=lambda n: arrays[n].nbytes)
+    for i, name in enumerate(order):
+        a, share = arrays[name], left / (len(order) - i)
+        if a.nbytes <= share or a.ndim == 0:
+            left -= a.nbytes
+            continue
+        keep[name] = max(1, int(share // (a.nbytes // len(a) + 8)))
+        left -= keep[name] * (a.nbytes // len(a) + 8)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if name in keep:
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), keep[name], replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 class MutedStderr:
@@ -460,9 +500,16 @@ def main() -> None:
                          "matches K2 / K3 produced for them in set-up; align: SparseImgAlign only (configs[1] read literally; the "
                          "default line carries it as value_sparse_align_only); full: configs[2] -- the whole track is the step "
                          "(the default run reports it as the extra key full_track instead)")
-    ap.add_argument("--extras", default="all",
-                    help="comma list of the extra legs to run at N=1 (all, none, or any of: f64, refine, full, full_easy, noise, "
-                         "config3, stream, rig, k0, dropin, pmc)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the extra legs (--extras), the rig replay and the gather "
+                         "timing of N > 1.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--extras", default=None,
+                    help="the extra legs of the full run at N=1, a comma list (all -- the default with --full --, none -- the "
+                         "default without --, or any of: f64, refine, full, full_easy, noise, config3, stream, rig, k0, dropin, "
+                         "pmc, cameras); a list of legs implies --full")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all: a fixed, seeded sample of the rows of larger outputs)")
     ap.add_argument("--k1-kernel", default="auto", choices=["auto", "workgroup"],
                     help="auto: svo_hip_sparse_align (the wave-per-frame kernel for batches >= 1024 of <= 192 patches, else the "
                          "workgroup-per-frame kernel); workgroup: always the workgroup-per-frame kernel")
@@ -471,7 +518,7 @@ def main() -> None:
                          f"(< {COMPACT_LIMIT} B) with the full object in {DETAILS_FILE}")
     ap.add_argument("--time-budget", type=float, default=330.0,
                     help="seconds since process start after which no further optional leg or counter pass is begun (0: no limit); "
-                         "the default run takes about four minutes on an MI355X box and stays below this")
+                         "a --full run takes about four minutes on an MI355X box and stays below this")
     ap.add_argument("--pmc-child", default="", help=argparse.SUPPRESS)
     ap.add_argument("--dump-result", default="", help=argparse.SUPPRESS)  # child of the f64_partials leg: poses + iteration counts
     args = ap.parse_args()
@@ -503,6 +550,12 @@ def main() -> None:
         flush_c_stdio()
     lib = capi.load()
     ev = Events(lib, dev)
+    if args.extras is None:
+        args.extras = "all" if args.full else "none"
+    elif args.extras != "none":
+        args.full = True  # a list of legs asks for the full run, restricted to them
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = True
     if args.extras == "all":
         extras = {"f64", "refine", "full", "full_easy", "long_scan", "noise", "config3", "stream", "rig", "k0", "dropin", "pmc", "cameras"}
     elif args.extras == "none":
@@ -627,13 +680,14 @@ def main() -> None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-        gather_stats = time_gather(gather, dist, dev, world, B, len(outs) > 1)
+        if args.full:
+            gather_stats = time_gather(gather, dist, dev, world, B, len(outs) > 1)
 
     # per-launch kernel duration from HIP events on the launch stream
     kernel_ms = float(np.mean([ev.ms(a, b) for a, b in marks])) if marks else float("nan")
 
     rig = None
-    if ("rig" in extras or use_dist) and not args.pmc_child:
+    if ("rig" in extras or (use_dist and args.full)) and not args.pmc_child:
         try:
             rig = rig_replay(ev, dev, dist if use_dist else None, world, rank)
         except Exception as e:  # never lose the headline line to an extra leg
@@ -649,6 +703,14 @@ def main() -> None:
     iters, n_tracked, alg_bytes = st["iters"], st["n_tracked"], st["alg_bytes"]
     k4_ms = float(np.mean([ev.ms(a, b) for a, b in marks4])) if marks4 else None
     po_last = pos[(counter[0] - 1) % len(outs)] if refine is not None else None
+    if args.dump_outputs:  # before any extra leg can touch the buffers
+        dumped = {"sparse_align": out}
+        if refine is not None:
+            dumped["pose_refine"] = po_last
+        if full is not None:
+            dumped.update({"full_track_match": full.last["match"], "full_track_pose": full.last["pose"],
+                           "full_track_seed_status": full.last["seed_status"], "full_track_seeds": full.seeds})
+        dump_outputs(args.dump_outputs, dumped)
     workload_name = args.workload
     if full is not None:
         workload_name = args.workload.replace("sparse_align", "full_track")

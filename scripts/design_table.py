@@ -17,7 +17,7 @@ def table(d: dict, src: str) -> str:
     L = []
     r = d["roofline"]
     B = d["config"]["frames_per_step_per_gpu"]
-    L.append(f"Source: `{src}` (`bench.py --steps {d.get('steps')} --warmup {d.get('warmup')}`: {d.get('steps')} timed steps of {B} frames).")
+    L.append(f"Source: `{src}` (`bench.py --full --steps {d.get('steps')} --warmup {d.get('warmup')}`: {d.get('steps')} timed steps of {B} frames).")
     L.append("")
     L.append("| kernel (per launch / step of 16 384 frames) | ms | algorithmic bytes per unit | GB/s | frac of 8 TB/s | counter traffic / algorithmic | VALU busy | wave cycles waiting |")
     L.append("|---|---|---|---|---|---|---|---|")

@@ -21,7 +21,7 @@ PY
 }
 echo "== the driver's command (last stdout line = the compact summary; the full object is bench_details.json)"
 (cd $R && (time python3 bench.py --gpus 1 --steps 20 --warmup 5) > $O/bench_driver_style_line.json 2> $O/bench_driver_style.err; cp bench_details.json $O/bench_driver_style_details.json)
-echo "== default bench"; (cd $R && (time python bench.py) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json)
+echo "== default bench"; (cd $R && (time python bench.py --full) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json)
 echo "== headline under kernel trace"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_align -o trace -- python $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --extras none > $O/align_bench_under_trace.json 2> $O/trace_align.err
 stats $O/trace_align $O/align_kernel_stats.csv

@@ -19,7 +19,7 @@ PY
 echo "== GPU suite"
 timeout 900 python -m pytest tests -q -m gpu 2>&1 | tail -6
 echo "== default bench"
-(time python bench.py) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json
+(time python bench.py --full) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json
 tail -c 800 $O/bench_default_line.json; echo; tail -4 $O/bench_default.err
 echo "== headline under kernel trace"
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_align -o trace -- python $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --extras none > $O/align_bench_under_trace.json 2> $O/trace_align.err)

@@ -9,7 +9,7 @@ echo "== the driver's command"
 (time python3 bench.py --gpus 1 --steps 20 --warmup 5) > $O/bench_driver_style_line.json 2> $O/bench_driver_style.err; cp bench_details.json $O/bench_driver_style_details.json
 tail -c 300 $O/bench_driver_style_line.json; echo; tail -4 $O/bench_driver_style.err
 echo "== default bench"
-(time python bench.py) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json
+(time python bench.py --full) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json
 tail -c 300 $O/bench_default_line.json; echo; tail -4 $O/bench_default.err
 python - <<'PY'
 import json

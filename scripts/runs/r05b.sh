@@ -24,7 +24,7 @@ timeout 900 python -m pytest tests -q -m gpu 2>&1 | tail -15
 echo "== 2. K1 width A/B (40 steps after 15 warm-ups, alternating)"
 bash scripts/k1_variants.sh main svo_hip_SIA_F32_ROWS main svo_hip_SIA_F32_ROWS main svo_hip_SIA_F32_ROWS -- --steps 40 --warmup 15
 echo "== 3. default bench"
-(time python bench.py) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json
+(time python bench.py --full) > $O/bench_default_line.json 2> $O/bench_default.err; cp bench_details.json $O/bench_default_details.json
 tail -c 1500 $O/bench_default_line.json; echo; tail -4 $O/bench_default.err
 echo "== 4. headline under kernel trace: default, then the reference-width build"
 for v in default f64; do

@@ -29,8 +29,13 @@ def sanitizer():
     return os.environ.get("SVO_EMU_SANITIZE", "")
 
 
+def llvm_bin():
+    """ROCm's LLVM tools: clang++, its sanitizer runtimes, and the llvm-symbolizer their reports need for source lines"""
+    return os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin")
+
+
 def sanitizer_runtime(kind):
-    cxx = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
+    cxx = os.path.join(llvm_bin(), "clang++")
     name = {"address": "asan", "thread": "tsan", "undefined": "ubsan_standalone"}[kind]
     out = subprocess.run([cxx, f"-print-file-name=libclang_rt.{name}-x86_64.so"], capture_output=True, text=True).stdout.strip()
     return out if os.path.isabs(out) and os.path.exists(out) else None

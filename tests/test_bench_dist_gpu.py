@@ -40,7 +40,7 @@ def test_rccl_path_runs_with_one_rank(gpu_device):
     env = dict(os.environ, SVO_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--batch", "512", "--no-cpu-baseline",
-                        "--extras", "rig"], env=env, capture_output=True, text=True, timeout=580)
+                        "--full", "--extras", "rig"], env=env, capture_output=True, text=True, timeout=580)
     assert p.returncode == 0, p.stderr[-3000:]
     r = _last_json(p.stdout)
     assert r["n_gpus"] == 1 and r["value"] > 0
@@ -59,7 +59,7 @@ def test_two_gpu_launch_from_plain_shell(gpu_device):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "512",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=880)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=880)
     assert p.returncode == 0, p.stderr[-3000:]
     r = _last_json(p.stdout)
     assert r["n_gpus"] == 2 and r["gather"]["bytes_gathered_per_step"] == 2 * 512 * 96

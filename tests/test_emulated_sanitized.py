@@ -24,6 +24,14 @@ SUBSET = ["tests/test_sparse_align_emulated.py::test_emulated_sparse_align_edge_
           "-q", "-x", "-p", "no:cacheprovider"]
 
 
+def _env(**kw):
+    """the child's environment: ROCm's LLVM tools first on PATH, so that the sanitizer finds llvm-symbolizer for the source
+    lines of its report whatever PATH the suite was started with"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from emu_build import llvm_bin
+    return dict(os.environ, PATH=llvm_bin() + os.pathsep + os.environ.get("PATH", ""), **kw)
+
+
 def _runtime_or_skip(kind):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from emu_build import sanitizer_runtime
@@ -47,7 +55,7 @@ def sweeps(tmp_path_factory, oracle, schedule_runs):
         log = str(tmp_path_factory.mktemp(kind) / "report")
         out = open(log + ".out", "w")
         procs[kind] = (subprocess.Popen([os.path.join(ROOT, "scripts", "emu_sanitize.sh"), kind, *SUBSET], stdout=out,
-                                        stderr=subprocess.STDOUT, cwd=ROOT, env=dict(os.environ, SVO_TSAN_LOG=log)), log)
+                                        stderr=subprocess.STDOUT, cwd=ROOT, env=_env(SVO_TSAN_LOG=log)), log)
     done = {}
 
     def result(kind):
@@ -90,7 +98,7 @@ def test_the_sanitizer_sees_a_kernel_leave_its_buffer():
         "p = lambda a: C.c_void_p(a.ctypes.data)\n"
         "emu.svo_hip_pyramid_build_tiled(C.byref(layout), p(store), 0, 1, p(img), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None)\n"
         "print('survived')\n")
-    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0", SVO_EMU_SANITIZE="address")
+    env = _env(LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0", SVO_EMU_SANITIZE="address")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode != 0 and "survived" not in r.stdout
     assert "heap-buffer-overflow" in r.stderr and "pyramid.hip" in r.stderr, r.stderr[-3000:]
@@ -127,7 +135,7 @@ def test_the_race_detector_sees_a_missing_barrier(tmp_path, mode, racy):
         f"assert lib.probe_neighbour_sum({mode}, a.ctypes.data, o.ctypes.data) == 0\n"
         "print('exact', int((o == a + np.roll(a, -1)).sum()))\n")
     log = str(tmp_path / "tsan")
-    env = dict(os.environ, LD_PRELOAD=rt, TSAN_OPTIONS=f"report_signal_unsafe=0:log_path={log}", SVO_EMU_SANITIZE="thread", OMP_NUM_THREADS="1")
+    env = _env(LD_PRELOAD=rt, TSAN_OPTIONS=f"report_signal_unsafe=0:log_path={log}", SVO_EMU_SANITIZE="thread", OMP_NUM_THREADS="1")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     n, text = _races(log)
     assert "exact" in r.stdout, r.stderr[-3000:]
@@ -152,7 +160,7 @@ def test_the_race_detector_between_workgroups(tmp_path, mode, between, racy):
         f"assert lib.probe_neighbour_sum({mode}, a.ctypes.data, o.ctypes.data) == 0\n"
         "print('exact', int((o[128:] == np.roll(a, -1) + 1).sum()))\n")
     log = str(tmp_path / "tsan")
-    env = dict(os.environ, LD_PRELOAD=rt, TSAN_OPTIONS=f"report_signal_unsafe=0:log_path={log}", SVO_EMU_SANITIZE="thread", OMP_NUM_THREADS="1",
+    env = _env(LD_PRELOAD=rt, TSAN_OPTIONS=f"report_signal_unsafe=0:log_path={log}", SVO_EMU_SANITIZE="thread", OMP_NUM_THREADS="1",
                SVO_EMU_TSAN_BETWEEN_WORKGROUPS=between)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     n, text = _races(log)
