@@ -116,6 +116,151 @@ void releaseMirror(const Map* map) {
   r.all.erase(it);
 }
 
+// ---- what the mirrored and the list-walking path share: only where their trials come from differs ---------------------
+// Trials / visits one mirrored batch can hold (status 1 beyond: the frame takes the list-walking path).
+// SVO_HIP_MIRROR_TRIALS overrides the trial capacity: the tests use it to force that hand-over.
+size_t mirrorTrialCap() {
+  static const long t_cap_override = [] { const char* v = std::getenv("SVO_HIP_MIRROR_TRIALS"); return v ? std::atol(v) : 0L; }();
+  return t_cap_override > 0 ? (size_t)t_cap_override : 4096;
+}
+// The visiting loop stops once more than maxFts cells have matched (:137-138): of ~300 cells with candidates it
+// typically sees the first ~125, and what lies behind the stop is never looked at (nor are its counters touched).
+// The first batch therefore takes the cells a success rate of 3 in 4 would need; should the loop run out of them before
+// it stops (it then has matched less than three quarters of the cells), a second batch takes the rest.
+// SVO_HIP_FIRST_BATCH_CELLS overrides the size of the first batch: the tests use it to force the second one.
+size_t firstBatchCells() {
+  static const long first_batch_override = [] { const char* v = std::getenv("SVO_HIP_FIRST_BATCH_CELLS"); return v ? std::atol(v) : 0L; }();
+  return first_batch_override > 0 ? (size_t)first_batch_override : (size_t)Config::maxFts() + 1 + ((size_t)Config::maxFts() + 1) / 3 + 8;
+}
+
+// The match kernels' results per trial, in the lane's arena: refined pixel [2], ok, reference observation, search level,
+// A_cur_ref [4] (host views, then device addresses)
+struct TrialBlocks {
+  double *px, *A, *d_px, *d_A; int32_t *ok, *ref, *lvl, *d_ok, *d_ref, *d_lvl;
+  void alloc(svo_hip::Arena& a, size_t n) {
+    px = a.alloc<double>(2 * n, &d_px); ok = a.alloc<int32_t>(n, &d_ok); ref = a.alloc<int32_t>(n, &d_ref);
+    lvl = a.alloc<int32_t>(n, &d_lvl); A = a.alloc<double>(4 * n, &d_A);
+  }
+};
+
+// The predicted pose refinement (svo_hip::Speculation) behind a batch's match kernels: its blocks in the lane's arena
+// -- the observations the selection gathers (never read by the host), then the results -- and its launches
+struct Prediction {
+  size_t cap;  // observations it can hold
+  double *d_sf, *d_spos, *d_T, *d_Cov, *d_stats; int32_t *d_slvl, *d_nsel, *d_sel, *d_ran, *d_flag; uint8_t* d_has;
+  volatile int32_t* flag;  // host view of d_flag; NULL on a mirrored arena (no host-visible signals)
+  size_t results_begin;    // arena offset of the results
+
+  Prediction() { std::memset(static_cast<void*>(this), 0, sizeof(*this)); }
+  void allocInputs(svo_hip::Arena& a, size_t n) {  // (before Arena::endInputs())
+    cap = n;
+    a.alloc<double>(3 * cap, &d_sf);
+    a.alloc<double>(3 * cap, &d_spos);
+    a.alloc<int32_t>(cap, &d_slvl);
+  }
+  // the results (behind the match results) and the lane's record `sp` of them.  The pose goes in and out like in the
+  // optimizer's own call; pose_from_device: it is overwritten on the stream, and sp.T_init is set when it is known.
+  void allocOutputs(svo_hip::Arena& a, const Frame& frame, svo_hip::Speculation& sp, bool pose_from_device) {
+    sp.frame_id = frame.id_;
+    sp.point.clear(); sp.px.clear(); sp.level.clear(); sp.trial.clear();
+    results_begin = a.used();
+    double* T = a.alloc<double>(12, &d_T);
+    hip_dropin::poseToRt(frame.T_f_w_, T);
+    if (!pose_from_device) std::copy(T, T + 12, sp.T_init);
+    sp.T = T;
+    sp.n_sel = a.alloc<int32_t>(1, &d_nsel);
+    sp.sel = a.alloc<int32_t>(cap, &d_sel);
+    sp.has_point = a.alloc<uint8_t>(cap, &d_has);
+    sp.Cov = a.alloc<double>(36, &d_Cov);
+    sp.stats = a.alloc<double>(4, &d_stats);
+    sp.ran = a.alloc<int32_t>(1, &d_ran);
+    if (a.mode() != svo_hip::Arena::MIRRORED) {
+      flag = a.alloc<int32_t>(1, &d_flag);
+      *flag = 0;
+    }
+    sp.reproj_thresh = Config::poseOptimThresh();
+    sp.n_iter = (int)Config::poseOptimNumIter();
+  }
+  // selection -> pose refinement behind the match kernels; select(*this, stream) launches svo_hip_select_matches or its
+  // _indirect form with d_flag as the signal.  Hybrid / mapped arena: the results land in host memory as the kernels
+  // write them, so on the lane's stream, and the selection kernel stores `flag` when it starts, i.e. when the match
+  // kernels are through: `wait` polls that instead of waiting for the stream.  Mirrored arena: behind the match results
+  // on the lane's second stream, so that `wait` for the lane's stream ends with the copy of the match results.
+  // (The wave kernel alone: a frame it hands over, ran == 2, is finished by the optimizer's drop-in.)
+  template <class Select>
+  void enqueue(svo_hip::Arena& a, svo_hip::Lane& lane, const svo_hip_camera& cam, svo_hip::Speculation& sp, bool wait,
+               Select select) const {
+    void* stream = lane.stream;
+    if (flag == NULL) {
+      stream = lane.stream_next;
+      svo_hip::check(svo_hip_event_record(lane.ev_results, lane.stream), "svo_hip_event_record");
+      svo_hip::check(svo_hip_stream_wait_event(stream, lane.ev_results), "svo_hip_stream_wait_event");
+    }
+    select(*this, stream);
+    svo_hip::check(svo_hip_pose_optimize_deferred(&cam, 1, d_nsel, (int)cap, d_sf, d_slvl, d_spos, d_has, sp.reproj_thresh,
+                                                  sp.n_iter, d_T, d_Cov, d_stats, d_ran, stream),
+                   "svo_hip_pose_optimize_deferred");
+    if (flag == NULL) a.downloadRange(results_begin, a.used(), stream);
+    sp.stream = stream;
+    sp.in_flight = true;  // beginCall() of the lane's next call (or the optimizer's drop-in) waits for it
+    if (wait && flag != NULL) svo_hip::spinUntil(flag, 1, lane.stream);
+    else if (wait) svo_hip::check(svo_hip_stream_sync(lane.stream), "svo_hip_stream_sync");
+  }
+};
+
+// The features the host selects for the prediction: what the device's selection must have picked, for the optimizer's
+// drop-in to check.  Published under the lane's mutex, in one piece (the lane's next call reads it under the same mutex).
+struct PredictionRecord {
+  std::vector<const void*> point;
+  std::vector<double> px;
+  std::vector<int32_t> level, trial;
+  void publish(svo_hip::Lane& lane) {
+    std::lock_guard<std::mutex> guard(lane.mut);
+    svo_hip::Speculation& sp = lane.spec;
+    sp.point.swap(point); sp.px.swap(px); sp.level.swap(level); sp.trial.swap(trial);
+    sp.valid = !sp.point.empty();
+  }
+};
+
+// One findMatchDirect trial: its index in the batch (-1: none), its result, Matcher::ref_ftr_ and A_cur_ref [2][2]
+// (row-major; read for an edgelet reference only)
+struct Trial {
+  int index; bool ok; Vector2d px; int level; const Feature* ref; const double* A;
+};
+enum TrialOutcome { TRIAL_FAILED, TRIAL_DELETED, TRIAL_MATCHED, TRIAL_PROMOTED /* matched, and now TYPE_GOOD */ };
+
+// Reprojector::reprojectCell's bookkeeping of one trial (:160-200): the point's counters and its deletion or promotion;
+// on success the frame's new Feature, also recorded in `pred` unless NULL
+TrialOutcome applyTrial(Map& map, Frame* frame, Point* pt, const Trial& t, PredictionRecord* pred) {
+  if (!t.ok) {
+    pt->n_failed_reproj_++;
+    if (pt->type_ == Point::TYPE_UNKNOWN && pt->n_failed_reproj_ > 15) { map.safeDeletePoint(pt); return TRIAL_DELETED; }
+    if (pt->type_ == Point::TYPE_CANDIDATE && pt->n_failed_reproj_ > 30) { map.point_candidates_.deleteCandidatePoint(pt); return TRIAL_DELETED; }
+    return TRIAL_FAILED;
+  }
+  TrialOutcome r = TRIAL_MATCHED;
+  pt->n_succeeded_reproj_++;
+  if (pt->type_ == Point::TYPE_UNKNOWN && pt->n_succeeded_reproj_ > 10) { pt->type_ = Point::TYPE_GOOD; r = TRIAL_PROMOTED; }
+  Feature* new_feature = new Feature(frame, t.px, t.level);
+  frame->addFeature(new_feature);
+  new_feature->point = pt;  // the point learns about this observation only if the frame becomes a keyframe
+  if (t.ref != NULL && t.ref->type == Feature::EDGELET) {
+    new_feature->type = Feature::EDGELET;
+    Matrix2d A_cur_ref;
+    A_cur_ref(0, 0) = t.A[0]; A_cur_ref(0, 1) = t.A[1];
+    A_cur_ref(1, 0) = t.A[2]; A_cur_ref(1, 1) = t.A[3];
+    new_feature->grad = A_cur_ref * t.ref->grad;
+    new_feature->grad.normalize();
+  }
+  if (pred != NULL) {
+    pred->point.push_back(pt);
+    pred->px.push_back(t.px[0]); pred->px.push_back(t.px[1]);
+    pred->level.push_back(t.level);
+    pred->trial.push_back(t.index);
+  }
+  return r;
+}
+
 // ---- one batch of the mirrored path: reproject_map -> match kernels -> selection -> predicted pose refinement ---------
 // The blocks of a batch in the lane's arena, and the launches on them.  Two users: reprojectMapMirrored's own call (fill
 // -> upload -> launch -> wait), and MirrorChain below, which adds the same blocks and launches to the call of
@@ -138,23 +283,17 @@ struct MirrorBatch {
   svo_hip_map_patch patch;
   int32_t* d_rank;
   svo_hip_frames ft;
-  double* h_frame_T;  // host view of the frame table's poses (the chain re-reads nothing from it; kept for symmetry)
-  double *d_sf, *d_spos; int32_t* d_slvl;
   svo_hip_reprojection out;
   int32_t* header;
-  const int32_t *h_point_cell, *h_kf_count, *h_vp, *h_vc, *h_vt, *h_ok, *h_ref, *h_lvl;
-  const double *h_px, *h_A;
-  double* d_A; int32_t *d_ok, *d_ref, *d_lvl;
-  double *d_T, *d_Cov, *d_stats; int32_t *d_nsel, *d_sel, *d_ran, *d_flag; uint8_t* d_has;
-  volatile int32_t* flag;
-  double* h_T;  // the predicted refinement's in/out pose block (host view)
-  size_t inputs_end, match_end, results_begin;
+  const int32_t *h_point_cell, *h_kf_count, *h_vp, *h_vc, *h_vt;
+  TrialBlocks trials;
+  Prediction pred;
+  size_t inputs_end, match_end;
 
   MirrorBatch() { std::memset(static_cast<void*>(&patch), 0, sizeof(patch)); clear(); }
   void clear() {
-    dev = NULL; lane = NULL; mm = NULL; predict = false; d_rank = NULL; h_frame_T = NULL; d_sf = d_spos = NULL; d_slvl = NULL;
-    std::memset(&out, 0, sizeof(out)); header = NULL; flag = NULL; d_flag = NULL; d_T = d_Cov = d_stats = NULL; h_T = NULL;
-    d_nsel = d_sel = d_ran = NULL; d_has = NULL; inputs_end = match_end = results_begin = 0; frame_id = -1;
+    dev = NULL; lane = NULL; mm = NULL; predict = false; d_rank = NULL;
+    std::memset(&out, 0, sizeof(out)); header = NULL; pred = Prediction(); inputs_end = match_end = 0; frame_id = -1;
   }
   size_t arenaBytes(size_t n_tab) const {
     return ((size_t)1 << 17) + mm->patchBytes() + mm->entries().size() * 8 + T_CAP * 128 + V_CAP * 16 + n_tab * 128;
@@ -165,12 +304,7 @@ struct MirrorBatch {
     int32_t* rank = a.alloc<int32_t>(rank_of.size(), &d_rank);
     std::copy(rank_of.begin(), rank_of.end(), rank);
     frames.emit(a, &ft);
-    const size_t cap = (size_t)Config::maxFts() + 1;
-    if (predict) {  // the predicted pose refinement's observations: gathered on the device, never read by the host
-      a.alloc<double>(3 * cap, &d_sf);
-      a.alloc<double>(3 * cap, &d_spos);
-      a.alloc<int32_t>(cap, &d_slvl);
-    }
+    if (predict) pred.allocInputs(a, (size_t)Config::maxFts() + 1);
   }
   // outputs the host reads (after Arena::endInputs()); sp: the lane's speculation record, filled when predict
   void allocOutputs(svo_hip::Arena& a, size_t n_tab, const FramePtr& frame, svo_hip::Speculation& sp, bool pose_from_device) {
@@ -183,40 +317,15 @@ struct MirrorBatch {
     h_vp = a.alloc<int32_t>(V_CAP, &out.d_visit_point);
     h_vc = a.alloc<int32_t>(V_CAP, &out.d_visit_cell);
     h_vt = a.alloc<int32_t>(V_CAP, &out.d_visit_trial);
-    h_px = a.alloc<double>(2 * T_CAP, &out.d_trial_px);
-    h_ok = a.alloc<int32_t>(T_CAP, &d_ok);
-    h_ref = a.alloc<int32_t>(T_CAP, &d_ref);
-    h_lvl = a.alloc<int32_t>(T_CAP, &d_lvl);
-    h_A = a.alloc<double>(4 * T_CAP, &d_A);
+    trials.alloc(a, T_CAP);
+    out.d_trial_px = trials.d_px;
     match_end = a.used();
     out.d_point_px = mm->pointPx();
     out.d_trial_cur = mm->trialCur(); out.d_trial_pos = mm->trialPos();
     out.d_trial_obs_begin = mm->trialObsBegin(); out.d_trial_obs_end = mm->trialObsEnd(); out.d_trial_cell = mm->trialCell();
-    results_begin = match_end;
-    if (predict) {
-      const size_t cap = (size_t)Config::maxFts() + 1;
-      sp.frame_id = frame->id_;
-      sp.point.clear(); sp.px.clear(); sp.level.clear(); sp.trial.clear();
-      results_begin = a.used();
-      h_T = a.alloc<double>(12, &d_T);
-      hip_dropin::poseToRt(frame->T_f_w_, h_T);  // (pose_from_device: overwritten on the stream, and T_init set when it is known)
-      if (!pose_from_device) std::copy(h_T, h_T + 12, sp.T_init);
-      sp.T = h_T;
-      sp.n_sel = a.alloc<int32_t>(1, &d_nsel);
-      sp.sel = a.alloc<int32_t>(cap, &d_sel);
-      sp.has_point = a.alloc<uint8_t>(cap, &d_has);
-      sp.Cov = a.alloc<double>(36, &d_Cov);
-      sp.stats = a.alloc<double>(4, &d_stats);
-      sp.ran = a.alloc<int32_t>(1, &d_ran);
-      if (a.mode() != svo_hip::Arena::MIRRORED) {
-        flag = a.alloc<int32_t>(1, &d_flag);
-        *flag = 0;
-      }
-      sp.reproj_thresh = Config::poseOptimThresh();
-      sp.n_iter = (int)Config::poseOptimNumIter();
-    }
+    if (predict) pred.allocOutputs(a, *frame, sp, pose_from_device);
   }
-  // reproject_map -> match kernels -> (predict, flag-capable arena) selection + pose refinement, on the lane's stream
+  // reproject_map -> match kernels, on the lane's stream
   void launchMatch(svo_hip::Arena& a) {
     const svo_hip_map dmap = mm->deviceMap();
     const svo_hip_features dobs = mm->deviceObs();
@@ -230,25 +339,19 @@ struct MirrorBatch {
                    "svo_hip_reproject_map");
     svo_hip::check(svo_hip_find_match_direct_indirect(&dev->layout(), dev->store(), &cam, &ft, (int)T_CAP, d_M, out.d_trial_cur,
                                                       out.d_trial_pos, out.d_trial_obs_begin, out.d_trial_obs_end, &dobs,
-                                                      Config::nPyrLevels(), align_max_iter, out.d_trial_px, d_ok, d_ref, d_lvl, d_A,
-                                                      NULL, ws, lane->workspace_bytes, lane->stream),
+                                                      Config::nPyrLevels(), align_max_iter, trials.d_px, trials.d_ok, trials.d_ref,
+                                                      trials.d_lvl, trials.d_A, NULL, ws, lane->workspace_bytes, lane->stream),
                    "svo_hip_find_match_direct_indirect");
     a.downloadRange(inputs_end, match_end, lane->stream);
   }
-  // hybrid / mapped arena: the selection kernel stores `flag` when it starts, i.e. when the match kernels are through;
-  // the host polls that, pose refinement follows on the same stream
-  void launchPredictionSameStream(svo_hip::Speculation& sp) {
-    const size_t cap = (size_t)Config::maxFts() + 1;
-    int32_t* const d_M = out.d_header + 3;
-    svo_hip::check(svo_hip_select_matches_indirect(&cam, (int)T_CAP, d_M, out.d_trial_cell, d_ok, out.d_trial_px, d_lvl,
-                                                   out.d_trial_pos, Config::maxFts(), d_nsel, d_sel, d_sf, d_slvl, d_spos, d_has,
-                                                   d_flag, 1, lane->stream),
-                   "svo_hip_select_matches_indirect");
-    svo_hip::check(svo_hip_pose_optimize_deferred(&cam, 1, d_nsel, (int)cap, d_sf, d_slvl, d_spos, d_has, sp.reproj_thresh,
-                                                  sp.n_iter, d_T, d_Cov, d_stats, d_ran, lane->stream),
-                   "svo_hip_pose_optimize_deferred");
-    sp.stream = lane->stream;
-    sp.in_flight = true;
+  // (predict) selection + pose refinement behind launchMatch
+  void launchPrediction(svo_hip::Arena& a, svo_hip::Speculation& sp, bool wait) {
+    pred.enqueue(a, *lane, cam, sp, wait, [this](const Prediction& p, void* stream) {
+      svo_hip::check(svo_hip_select_matches_indirect(&cam, (int)T_CAP, out.d_header + 3, out.d_trial_cell, trials.d_ok, trials.d_px,
+                                                     trials.d_lvl, out.d_trial_pos, Config::maxFts(), p.d_nsel, p.d_sel, p.d_sf,
+                                                     p.d_slvl, p.d_spos, p.d_has, p.d_flag, p.d_flag != NULL ? 1 : 0, stream),
+                     "svo_hip_select_matches_indirect");
+    });
   }
 };
 
@@ -358,14 +461,14 @@ class MirrorChain : public hip_dropin::FrameChain {
   }
   void enqueue(const double* d_T_cur_ref) {
     svo_hip::check(svo_hip_frame_pose_compose(d_T_cur_ref, d_qt_, d_qt_ + 4, const_cast<double*>(b_.ft.d_T_f_w), b_.i_cur,
-                                              b_.predict ? b_.d_T : NULL, d_Tcomp_, &b_.cam, (int)n_tab_, (int)n_kf_, d_key_pos_,
+                                              b_.predict ? b_.pred.d_T : NULL, d_Tcomp_, &b_.cam, (int)n_tab_, (int)n_kf_, d_key_pos_,
                                               d_key_valid_, (int)options_.max_n_kfs, b_.d_rank, d_rank_host_, d_flag_k1_, 1,
                                               b_.lane->stream),
                    "svo_hip_frame_pose_compose");
     b_.launchMatch(b_.lane->arena);
     svo_hip::Speculation& sp = b_.lane->spec;
     if (b_.predict) {
-      b_.launchPredictionSameStream(sp);
+      b_.launchPrediction(b_.lane->arena, sp, false);  // (adopt() waits for the signal)
     } else {
       sp.stream = b_.lane->stream;  // (beginCall() of the lane's next call drains the stream before it refills the arena)
       sp.in_flight = true;
@@ -422,7 +525,7 @@ class MirrorChain : public hip_dropin::FrameChain {
       {
         svo_hip::StageTimer stage_timer(dev, lane, svo_hip::Device::STAGE_REPROJECT);
         stage_timer.device(0);
-        if (b_.predict) svo_hip::spinUntil(b_.flag, 1, lane.stream);
+        if (b_.predict) svo_hip::spinUntil(b_.pred.flag, 1, lane.stream);
         else dev.finish(lane);
         stage_timer.unmarshal();
       }
@@ -437,15 +540,6 @@ class MirrorChain : public hip_dropin::FrameChain {
     ranked = ranked_now;
     n_tab = n_tab_;
     return true;
-  }
-
-  static size_t mirrorTrialCap() {
-    static const long t_cap_override = [] { const char* v = std::getenv("SVO_HIP_MIRROR_TRIALS"); return v ? std::atol(v) : 0L; }();
-    return t_cap_override > 0 ? (size_t)t_cap_override : 4096;
-  }
-  static size_t firstBatchCells() {
-    static const long first_batch_override = [] { const char* v = std::getenv("SVO_HIP_FIRST_BATCH_CELLS"); return v ? std::atol(v) : 0L; }();
-    return first_batch_override > 0 ? (size_t)first_batch_override : (size_t)Config::maxFts() + 1 + ((size_t)Config::maxFts() + 1) / 3 + 8;
   }
 
  private:
@@ -486,9 +580,7 @@ bool reprojectMapMirrored(const FramePtr& frame, std::vector<std::pair<FramePtr,
                           size_t& n_trials_, MirrorChain<GridT>* chain) {
   using namespace hip_dropin;
   const size_t n_cells = grid_.cells.size();
-  // trials / visits one batch can hold (status 1 beyond: the frame takes the list-walking path; SVO_HIP_MIRROR_TRIALS
-  // overrides the trial capacity: the tests use it to force that hand-over)
-  const size_t T_CAP = MirrorChain<GridT>::mirrorTrialCap();
+  const size_t T_CAP = mirrorTrialCap();
   if (n_cells > (size_t)SVO_HIP_REPROJ_MAX_CELLS || options_.max_n_kfs > 16) return false;
   MapMirror& mm = mirrorOf(&map_);
   ++mm.stats.calls;
@@ -553,31 +645,8 @@ bool reprojectMapMirrored(const FramePtr& frame, std::vector<std::pair<FramePtr,
     stage_timer.device(a.used());
     a.uploadAll(lane.stream);
     b.launchMatch(a);
-    if (predict && b.flag != NULL) {
-      b.launchPredictionSameStream(sp);
-      svo_hip::spinUntil(b.flag, 1, lane.stream);
-    } else if (predict) {
-      // mirrored arena: behind the match results on the lane's second stream, so that the wait below ends with the copy
-      // of the match results
-      const size_t cap = (size_t)Config::maxFts() + 1;
-      int32_t* const d_M = b.out.d_header + 3;
-      void* const next = lane.stream_next;
-      svo_hip::check(svo_hip_event_record(lane.ev_results, lane.stream), "svo_hip_event_record");
-      svo_hip::check(svo_hip_stream_wait_event(next, lane.ev_results), "svo_hip_stream_wait_event");
-      svo_hip::check(svo_hip_select_matches_indirect(&b.cam, (int)T_CAP, d_M, b.out.d_trial_cell, b.d_ok, b.out.d_trial_px, b.d_lvl,
-                                                     b.out.d_trial_pos, Config::maxFts(), b.d_nsel, b.d_sel, b.d_sf, b.d_slvl, b.d_spos,
-                                                     b.d_has, NULL, 0, next),
-                     "svo_hip_select_matches_indirect");
-      svo_hip::check(svo_hip_pose_optimize_deferred(&b.cam, 1, b.d_nsel, (int)cap, b.d_sf, b.d_slvl, b.d_spos, b.d_has, sp.reproj_thresh,
-                                                    sp.n_iter, b.d_T, b.d_Cov, b.d_stats, b.d_ran, next),
-                     "svo_hip_pose_optimize_deferred");
-      a.downloadRange(b.results_begin, a.used(), next);
-      sp.stream = next;
-      sp.in_flight = true;
-      svo_hip::check(svo_hip_stream_sync(lane.stream), "svo_hip_stream_sync");
-    } else {
-      svo_hip::check(svo_hip_stream_sync(lane.stream), "svo_hip_stream_sync");
-    }
+    if (predict) b.launchPrediction(a, sp, true);
+    else svo_hip::check(svo_hip_stream_sync(lane.stream), "svo_hip_stream_sync");
     stage_timer.unmarshal();
     if (b.header[0] != 0) {  // a capacity was exceeded (or, -1, the kernel never ran): drop what was enqueued behind it
       if (predict) {
@@ -590,8 +659,7 @@ bool reprojectMapMirrored(const FramePtr& frame, std::vector<std::pair<FramePtr,
     return true;
   };
 
-  // The first batch takes the cells a success rate of 3 in 4 would need (see the list-walking path)
-  if (!adopted && !runBatch(0, MirrorChain<GridT>::firstBatchCells())) { ++mm.stats.fallbacks; mm.invalidate(); return false; }
+  if (!adopted && !runBatch(0, firstBatchCells())) { ++mm.stats.fallbacks; mm.invalidate(); return false; }
   // the tables of the batch in flight (host addresses of arena blocks)
   size_t view_V = (size_t)batch.header[2], view_end_cell = (size_t)batch.header[4];
   const int32_t* point_cell = batch.h_point_cell;
@@ -621,11 +689,8 @@ bool reprojectMapMirrored(const FramePtr& frame, std::vector<std::pair<FramePtr,
   }
 
   // ---- 4. per cell, in the shuffled order: the best-quality point that matched (:131-139, 151-200)
-  svo_hip::Speculation& sp = lane.spec;
   std::vector<int32_t> selected;
-  std::vector<const void*> pred_point;  // what the device's selection must have picked, for the optimizer's drop-in to check
-  std::vector<double> pred_px;
-  std::vector<int32_t> pred_level, pred_trial;
+  PredictionRecord record;
   size_t v = 0;
   for (size_t i = 0; i < n_cells; ++i) {
     if (i == view_end_cell) {
@@ -644,44 +709,23 @@ bool reprojectMapMirrored(const FramePtr& frame, std::vector<std::pair<FramePtr,
       const int32_t e = batch.h_vp[v];
       Point* pt = mm.entries()[(size_t)e].pt;
       const int m = batch.h_vt[v];
-      if (!(m >= 0 && batch.h_ok[m] != 0)) {
-        pt->n_failed_reproj_++;
-        if (pt->type_ == Point::TYPE_UNKNOWN && pt->n_failed_reproj_ > 15) { map_.safeDeletePoint(pt); mm.markDead(e); }
-        if (pt->type_ == Point::TYPE_CANDIDATE && pt->n_failed_reproj_ > 30) { map_.point_candidates_.deleteCandidatePoint(pt); mm.markDead(e); }
-        continue;
+      const TrialBlocks& r = batch.trials;  // (what a failed trial returned is not read)
+      Trial t = {m, m >= 0 && r.ok[m] != 0, Vector2d::Zero(), 0, NULL, NULL};
+      if (t.ok) {
+        t.px = Vector2d(r.px[2 * m], r.px[2 * m + 1]); t.level = r.lvl[m]; t.A = r.A + 4 * m;
+        t.ref = r.ref[m] >= 0 ? mm.obsFeature(r.ref[m]) : NULL;
       }
-      pt->n_succeeded_reproj_++;
-      if (pt->type_ == Point::TYPE_UNKNOWN && pt->n_succeeded_reproj_ > 10) { pt->type_ = Point::TYPE_GOOD; mm.markType(e, 3); }
-      const Vector2d px(batch.h_px[2 * m], batch.h_px[2 * m + 1]);
-      Feature* new_feature = new Feature(frame.get(), px, batch.h_lvl[m]);
-      frame->addFeature(new_feature);
-      new_feature->point = pt;
-      const Feature* ref_ftr = batch.h_ref[m] >= 0 ? mm.obsFeature(batch.h_ref[m]) : NULL;
-      if (ref_ftr != NULL && ref_ftr->type == Feature::EDGELET) {
-        new_feature->type = Feature::EDGELET;
-        Matrix2d A_cur_ref;
-        A_cur_ref(0, 0) = batch.h_A[4 * m]; A_cur_ref(0, 1) = batch.h_A[4 * m + 1];
-        A_cur_ref(1, 0) = batch.h_A[4 * m + 2]; A_cur_ref(1, 1) = batch.h_A[4 * m + 3];
-        new_feature->grad = A_cur_ref * ref_ftr->grad;
-        new_feature->grad.normalize();
-      }
-      if (predict) {
-        pred_point.push_back(pt);
-        pred_px.push_back(px[0]); pred_px.push_back(px[1]);
-        pred_level.push_back(batch.h_lvl[m]);
-        pred_trial.push_back(m);
-      }
+      const TrialOutcome outcome = applyTrial(map_, frame.get(), pt, t, predict ? &record : NULL);
+      if (outcome == TRIAL_DELETED) mm.markDead(e);
+      if (outcome == TRIAL_PROMOTED) mm.markType(e, 3);
+      if (outcome < TRIAL_MATCHED) continue;
       selected.push_back(e);
       matched = true;
     }
     if (matched) ++n_matches_;
     if (n_matches_ > (size_t)Config::maxFts()) break;
   }
-  if (predict) {  // published under the lane's mutex, in one piece (the lane's next call reads it under the same mutex)
-    std::lock_guard<std::mutex> guard(lane.mut);
-    sp.point.swap(pred_point); sp.px.swap(pred_px); sp.level.swap(pred_level); sp.trial.swap(pred_trial);
-    sp.valid = !sp.point.empty();
-  }
+  if (predict) record.publish(lane);
   mm.watch(selected);  // FrameHandlerBase::optimizeStructure may move these before the next frame
   return true;
 }
@@ -823,20 +867,10 @@ void Reprojector::reprojectMap(FramePtr frame, std::vector<std::pair<FramePtr, s
   std::vector<double> R_px, R_A;                 // [trial][2], [trial][4]
   std::vector<int32_t> R_ok, R_lvl;              // [trial]
   std::vector<Feature*> R_ref;                   // [trial] Matcher::ref_ftr_
-  std::vector<const void*> pred_point;  // the prediction's features as the host selects them (published at the end)
-  std::vector<double> pred_px;
-  std::vector<int32_t> pred_level, pred_trial;
+  PredictionRecord record;
   bool predict = false;             // pose refinement of this frame has been enqueued behind the match kernels
   svo_hip::Lane* spec_lane = NULL;  // ... on this lane
   size_t enumerated_end = 0;        // cells [0, enumerated_end) of the visiting order have their trials
-  // The visiting loop stops once more than maxFts cells have matched (:137-138): of ~300 cells with candidates it
-  // typically sees the first ~125, and what lies behind the stop is never looked at (nor are its counters touched).
-  // The first batch therefore takes the cells a success rate of 3 in 4 would need; should step 4 run out of them before
-  // it stops (it then has matched less than three quarters of the cells), a second batch takes the rest.
-  // (SVO_HIP_FIRST_BATCH_CELLS overrides the size of the first batch: the tests use it to force the second one)
-  static const long first_batch_override = [] { const char* v = std::getenv("SVO_HIP_FIRST_BATCH_CELLS"); return v ? std::atol(v) : 0L; }();
-  const size_t first_batch_cells = first_batch_override > 0 ? (size_t)first_batch_override
-                                                            : (size_t)Config::maxFts() + 1 + ((size_t)Config::maxFts() + 1) / 3 + 8;
   // [first_cell, return value): the cells whose candidates were listed and matched
   auto runBatch = [&](const size_t first_cell, const size_t max_cells_with_trials) -> size_t {
     using namespace hip_dropin;
@@ -917,51 +951,18 @@ void Reprojector::reprojectMap(FramePtr frame, std::vector<std::pair<FramePtr, s
       ptr[M] = (int32_t)o;
       svo_hip_frames ft;
       frames.emit(a, &ft);
-      // the predicted pose refinement's observations: gathered on the device, never read by the host
-      double *d_sf = NULL, *d_spos = NULL;
-      int32_t* d_slvl = NULL;
-      if (predict) {
-        a.alloc<double>(3 * cap, &d_sf);
-        a.alloc<double>(3 * cap, &d_spos);
-        a.alloc<int32_t>(cap, &d_slvl);
-      }
+      Prediction pred;
+      if (predict) pred.allocInputs(a, cap);
       a.endInputs();
       const size_t inputs_end = a.used();
-
-      double *d_px, *d_A; int32_t *d_ok, *d_ref, *d_lvl;
-      double* px = a.alloc<double>(2 * M, &d_px);  // in: projection, out: refined pixel (uploadAll + download)
-      std::copy(px_in.begin(), px_in.end(), px);
-      int32_t* ok = a.alloc<int32_t>(M, &d_ok);
-      int32_t* ref = a.alloc<int32_t>(M, &d_ref);
-      int32_t* lvl = a.alloc<int32_t>(M, &d_lvl);
-      double* A = a.alloc<double>(4 * M, &d_A);
+      TrialBlocks res;
+      res.alloc(a, M);
+      std::copy(px_in.begin(), px_in.end(), res.px);  // in: projection, out: refined pixel (uploadAll + download)
       const size_t match_end = a.used();
-
-      double *d_T = NULL, *d_Cov = NULL, *d_stats = NULL;
-      int32_t *d_nsel = NULL, *d_sel = NULL, *d_ran = NULL, *d_flag = NULL;
-      volatile int32_t* flag = NULL;
-      uint8_t* d_has = NULL;
-      size_t results_begin = match_end;
       svo_hip::Speculation& sp = lane.spec;
       if (predict) {
         spec_lane = &lane;
-        sp.frame_id = frame->id_;
-        sp.point.clear(); sp.px.clear(); sp.level.clear(); sp.trial.clear();
-        results_begin = a.used();
-        // what comes back: the pose goes in and out like in the optimizer's own call
-        double* T = a.alloc<double>(12, &d_T);
-        poseToRt(frame->T_f_w_, T);
-        std::copy(T, T + 12, sp.T_init);
-        sp.T = T;
-        sp.n_sel = a.alloc<int32_t>(1, &d_nsel);
-        sp.sel = a.alloc<int32_t>(cap, &d_sel);
-        sp.has_point = a.alloc<uint8_t>(cap, &d_has);
-        sp.Cov = a.alloc<double>(36, &d_Cov);
-        sp.stats = a.alloc<double>(4, &d_stats);
-        sp.ran = a.alloc<int32_t>(1, &d_ran);
-        if (a.mode() != svo_hip::Arena::MIRRORED) flag = a.alloc<int32_t>(1, &d_flag);
-        sp.reproj_thresh = Config::poseOptimThresh();
-        sp.n_iter = (int)Config::poseOptimNumIter();
+        pred.allocOutputs(a, *frame, sp, false);
       }
 
       const svo_hip_camera cam = cameraOf(frame->cam_);
@@ -969,56 +970,30 @@ void Reprojector::reprojectMap(FramePtr frame, std::vector<std::pair<FramePtr, s
       stage_timer.device(a.used());
       a.uploadAll(lane.stream);
       svo_hip::check(svo_hip_find_match_direct(&dev.layout(), dev.store(), &cam, &ft, (int)M, d_cur, d_pos, d_ptr, &obs.dev,
-                                               Config::nPyrLevels(), matcher_.options_.align_max_iter, d_px, d_ok, d_ref, d_lvl,
-                                               d_A, NULL, ws, lane.workspace_bytes, lane.stream),
+                                               Config::nPyrLevels(), matcher_.options_.align_max_iter, res.d_px, res.d_ok,
+                                               res.d_ref, res.d_lvl, res.d_A, NULL, ws, lane.workspace_bytes, lane.stream),
                      "svo_hip_find_match_direct");
       a.downloadRange(inputs_end, match_end, lane.stream);
-      if (predict && flag != NULL) {
-        // Results land in host memory as the kernels write them (hybrid / mapped arena): the selection kernel stores
-        // `flag` when it starts, i.e. when the match kernels are through, and the host polls that instead of waiting
-        // for the stream -- pose refinement follows on the same stream, no event, no second queue.
-        *flag = 0;
-        svo_hip::check(svo_hip_select_matches(&cam, (int)M, d_cell, d_ok, d_px, d_lvl, d_pos, Config::maxFts(), d_nsel, d_sel, d_sf,
-                                              d_slvl, d_spos, d_has, d_flag, 1, lane.stream),
-                       "svo_hip_select_matches");
-        // (the wave kernel alone: a frame it hands over, ran == 2, is finished by the optimizer's drop-in)
-        svo_hip::check(svo_hip_pose_optimize_deferred(&cam, 1, d_nsel, (int)cap, d_sf, d_slvl, d_spos, d_has, sp.reproj_thresh,
-                                                      sp.n_iter, d_T, d_Cov, d_stats, d_ran, lane.stream),
-                       "svo_hip_pose_optimize_deferred");
-        sp.stream = lane.stream;
-        sp.in_flight = true;  // beginCall() of the lane's next call (or the optimizer's drop-in) waits for it
-        svo_hip::spinUntil(flag, 1, lane.stream);
-      } else if (predict) {
-        // mirrored arena: behind the match results on the lane's second stream, so that the wait below ends with the
-        // copy of the match results
-        void* const next = lane.stream_next;
-        svo_hip::check(svo_hip_event_record(lane.ev_results, lane.stream), "svo_hip_event_record");
-        svo_hip::check(svo_hip_stream_wait_event(next, lane.ev_results), "svo_hip_stream_wait_event");
-        svo_hip::check(svo_hip_select_matches(&cam, (int)M, d_cell, d_ok, d_px, d_lvl, d_pos, Config::maxFts(), d_nsel, d_sel, d_sf,
-                                              d_slvl, d_spos, d_has, NULL, 0, next),
-                       "svo_hip_select_matches");
-        svo_hip::check(svo_hip_pose_optimize_deferred(&cam, 1, d_nsel, (int)cap, d_sf, d_slvl, d_spos, d_has, sp.reproj_thresh,
-                                                      sp.n_iter, d_T, d_Cov, d_stats, d_ran, next),
-                       "svo_hip_pose_optimize_deferred");
-        a.downloadRange(results_begin, a.used(), next);
-        sp.stream = next;
-        sp.in_flight = true;
+      if (predict)
+        pred.enqueue(a, lane, cam, sp, true, [&](const Prediction& p, void* stream) {
+          svo_hip::check(svo_hip_select_matches(&cam, (int)M, d_cell, res.d_ok, res.d_px, res.d_lvl, d_pos, Config::maxFts(), p.d_nsel,
+                                                p.d_sel, p.d_sf, p.d_slvl, p.d_spos, p.d_has, p.d_flag, p.d_flag != NULL ? 1 : 0, stream),
+                         "svo_hip_select_matches");
+        });
+      else
         svo_hip::check(svo_hip_stream_sync(lane.stream), "svo_hip_stream_sync");
-      } else {
-        svo_hip::check(svo_hip_stream_sync(lane.stream), "svo_hip_stream_sync");
-      }
       stage_timer.unmarshal();
 
       // out of the arena: a later batch (or anything else on this lane) may reuse it
-      R_px.insert(R_px.end(), px, px + 2 * M);
-      R_A.insert(R_A.end(), A, A + 4 * M);
-      R_ok.insert(R_ok.end(), ok, ok + M);
-      R_lvl.insert(R_lvl.end(), lvl, lvl + M);
-      for (size_t m = 0; m < M; ++m) R_ref.push_back(ref[m] >= 0 ? obs_ftr[ref[m]] : NULL);
+      R_px.insert(R_px.end(), res.px, res.px + 2 * M);
+      R_A.insert(R_A.end(), res.A, res.A + 4 * M);
+      R_ok.insert(R_ok.end(), res.ok, res.ok + M);
+      R_lvl.insert(R_lvl.end(), res.lvl, res.lvl + M);
+      for (size_t m = 0; m < M; ++m) R_ref.push_back(res.ref[m] >= 0 ? obs_ftr[res.ref[m]] : NULL);
     }
     return end_cell;
   };
-  if (options_.find_match_direct) enumerated_end = runBatch(0, first_batch_cells);
+  if (options_.find_match_direct) enumerated_end = runBatch(0, firstBatchCells());
 
   // ---- 4. per cell, in the shuffled order: the best-quality point that matched ---------------
   for (size_t i = 0; i < grid_.cells.size(); ++i) {
@@ -1036,57 +1011,20 @@ void Reprojector::reprojectMap(FramePtr frame, std::vector<std::pair<FramePtr, s
       ++n_trials_;
       Point* pt = it->pt;
       if (pt->type_ == Point::TYPE_DELETED) { it = cell.erase(it); continue; }
-      struct { int trial; bool ok; Vector2d px; int search_level; Feature* ref_ftr; } r;
+      Trial t = {-1, true, it->px, 0, NULL, NULL};  // (without find_match_direct: accept the projection as it is)
       if (options_.find_match_direct) {
         if (v >= visit_begin[i + 1]) throw std::logic_error("Reprojector: candidate without a device trial");
-        r.trial = visit[v++];
-        const int m = r.trial;
-        r.ok = m >= 0 && R_ok[m] != 0;
-        r.px = m >= 0 ? Vector2d(R_px[2 * m], R_px[2 * m + 1]) : it->px;
-        r.search_level = m >= 0 ? R_lvl[m] : 0;
-        r.ref_ftr = m >= 0 ? R_ref[m] : NULL;
-      } else {  // accept the projection as it is
-        r.trial = -1; r.ok = true; r.px = it->px; r.search_level = 0; r.ref_ftr = NULL;
+        const int m = t.index = visit[v++];
+        t.ok = m >= 0 && R_ok[m] != 0;
+        if (m >= 0) { t.px = Vector2d(R_px[2 * m], R_px[2 * m + 1]); t.level = R_lvl[m]; t.ref = R_ref[m]; t.A = &R_A[4 * m]; }
       }
-      if (!r.ok) {
-        pt->n_failed_reproj_++;
-        if (pt->type_ == Point::TYPE_UNKNOWN && pt->n_failed_reproj_ > 15) map_.safeDeletePoint(pt);
-        if (pt->type_ == Point::TYPE_CANDIDATE && pt->n_failed_reproj_ > 30) map_.point_candidates_.deleteCandidatePoint(pt);
-        it = cell.erase(it);
-        continue;
-      }
-      pt->n_succeeded_reproj_++;
-      if (pt->type_ == Point::TYPE_UNKNOWN && pt->n_succeeded_reproj_ > 10) pt->type_ = Point::TYPE_GOOD;
-
-      Feature* new_feature = new Feature(frame.get(), r.px, r.search_level);
-      frame->addFeature(new_feature);
-      new_feature->point = pt;  // the point learns about this observation only if the frame becomes a keyframe
-      if (r.ref_ftr != NULL && r.ref_ftr->type == Feature::EDGELET) {
-        new_feature->type = Feature::EDGELET;
-        Matrix2d A_cur_ref;
-        A_cur_ref(0, 0) = R_A[4 * r.trial]; A_cur_ref(0, 1) = R_A[4 * r.trial + 1];
-        A_cur_ref(1, 0) = R_A[4 * r.trial + 2]; A_cur_ref(1, 1) = R_A[4 * r.trial + 3];
-        new_feature->grad = A_cur_ref * r.ref_ftr->grad;
-        new_feature->grad.normalize();
-      }
-      if (predict) {  // what the device's selection must have picked, for the optimizer's drop-in to check
-        pred_point.push_back(pt);
-        pred_px.push_back(r.px[0]); pred_px.push_back(r.px[1]);
-        pred_level.push_back(r.search_level);
-        pred_trial.push_back(r.trial);
-      }
+      matched = applyTrial(map_, frame.get(), pt, t, predict ? &record : NULL) >= TRIAL_MATCHED;  // at most one feature per cell
       it = cell.erase(it);
-      matched = true;  // at most one feature per cell
     }
     if (matched) ++n_matches_;
     if (n_matches_ > (size_t)Config::maxFts()) break;
   }
-  if (predict) {  // published under the lane's mutex, in one piece
-    std::lock_guard<std::mutex> guard(spec_lane->mut);
-    svo_hip::Speculation& sp = spec_lane->spec;
-    sp.point.swap(pred_point); sp.px.swap(pred_px); sp.level.swap(pred_level); sp.trial.swap(pred_trial);
-    sp.valid = !sp.point.empty();
-  }
+  if (predict) record.publish(*spec_lane);
   SVO_STOP_TIMER("feature_align");
 }
 
