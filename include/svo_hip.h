@@ -748,6 +748,67 @@ int svo_hip_fast_detect(const svo_hip_pyr_layout* layout, const uint8_t* d_store
                         double detection_threshold, int32_t* d_corner_xy, int32_t* d_corner_level,
                         float* d_corner_score, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K8: two-view bootstrap, tracking (initialization.cpp) ------------------------------------------------ */
+/*
+ * Batched initialization::trackKlt up to the status vector (svo/src/initialization.cpp:136-147: the call of
+ * cv::calcOpticalFlowPyrLK with a 30 x 30 window, maxLevel 4, 30 iterations / eps 0.001 and
+ * OPTFLOW_USE_INITIAL_FLOW) for n_pairs (reference frame, current frame) pairs of store slots and n_pts points each.
+ * Not OpenCV's bits: Bouguet's pyramidal Lucas-Kanade as OpenCV documents it, in f32, on this library's pyramid
+ * (vk::halfSample levels instead of Gaussian pyrDown; no padding -- every pixel fetch clamps its integer coordinates
+ * to the level, so a level is continued by its border pixels and the derivatives are those of the continued image;
+ * f32, multiply-adds possibly fused, instead of 14-bit fixed point).  With W = win_size, L = max_level, h = (W - 1) / 2, per point:
+ *   q = px_cur_in / 2^L; for l = L .. 0 (q *= 2 between levels), p = px_ref / 2^l:
+ *   - template: window pixel (i, j) is the reference level sampled bilinearly at p - h + (j, i); Ix, Iy are the
+ *     Scharr derivatives (rows [3 10 3] / 32 against [-1 0 1]) sampled bilinearly at the same positions;
+ *     a11 = sum Ix^2, a12 = sum Ix Iy, a22 = sum Iy^2, D = a11 a22 - a12^2,
+ *     min_eig = (a11 + a22 - sqrt((a11 - a22)^2 + 4 a12^2)) / (2 W^2).  min_eig < min_eig_threshold or
+ *     D < FLT_EPSILON: at level 0 the point is lost (status 0), a coarser level is skipped (q unchanged);
+ *   - bounds: before the template is sampled (at p) and before every sampling of the current level (at q), if
+ *     floor(. - h) is < -W or >= the level's width / height in either axis (or not finite): level 0 -> lost,
+ *     coarser -> the level is left;
+ *   - at most max_iter iterations: J = current level sampled at q - h + (j, i), b1 = sum (J - I) Ix,
+ *     b2 = sum (J - I) Iy, delta = ((a12 b2 - a22 b1) / D, (a12 b1 - a11 b2) / D), q += delta; stop when
+ *     |delta|^2 <= eps^2; from the second iteration on, when |delta + delta_prev| < 0.01 in both axes,
+ *     q -= delta / 2 and stop;
+ *   - error = mean |J - I| over the window at the final level-0 position (itself subject to the bounds test).
+ *   d_ref_slot / d_cur_slot [n_pairs]   store slots of the two frames
+ *   d_px_ref [n_pairs][n_pts][2] f32    cv::Point2f px_ref (level-0 pixels)
+ *   d_px_cur [n_pairs][n_pts][2] f32    in: the initial flow (px_cur of the previous call, :39 / :147), out: px_cur
+ *   d_status [n_pairs][n_pts] u8        in: 0 = lost before this call -- none of the point's outputs is touched (the
+ *                                       batched form of the erase loop, :154-168); out: 1 tracked, 0 lost
+ *   d_error  [n_pairs][n_pts] f32       0 where the point is lost by this call
+ * One wave64 per point; sums in a fixed order: the same call gives the same bits.  Limits: win_size 30 is the only
+ * window implemented (any other value: SVO_HIP_ERANGE), n_pts <= 1024 (SVO_HIP_ERANGE), max_level <
+ * layout->n_levels (SVO_HIP_EINVAL).  n_pairs * n_pts == 0 is a successful no-op.
+ */
+typedef struct svo_hip_klt_params {
+  int32_t win_size;        /* klt_win_size, 30                                        */
+  int32_t max_level;       /* maxLevel, 4: levels 0..4 of the store are used          */
+  int32_t max_iter;        /* klt_max_iter, 30                                        */
+  float eps;               /* klt_eps, 0.001                                          */
+  float min_eig_threshold; /* calcOpticalFlowPyrLK's default minEigThreshold, 1e-4    */
+} svo_hip_klt_params;
+/* host-only: the reference's values (30, 4, 30, 1e-3, 1e-4) */
+int svo_hip_klt_params_default(svo_hip_klt_params* out);
+int svo_hip_klt_track(const svo_hip_pyr_layout* layout, const uint8_t* d_store, int n_pairs,
+                      const int32_t* d_ref_slot, const int32_t* d_cur_slot, int n_pts, const float* d_px_ref,
+                      float* d_px_cur, uint8_t* d_status, float* d_error, const svo_hip_klt_params* params,
+                      void* stream);
+/*
+ * The rest of trackKlt and the numbers KltHomographyInit::addSecondFrame gates on (initialization.cpp:163-164,
+ * :48-53), per pair on the device:
+ *   d_f_cur [n_pairs][n_pts][3]    frame_cur->c2f(px_cur): the unit bearing, as svo_hip_cam2world forms it
+ *   d_disparity [n_pairs][n_pts]   Vector2d(px_ref - px_cur).norm(): f32 differences, f64 norm
+ *                                  (both 0 where d_status is 0)
+ *   d_n_tracked [n_pairs]          disparities_.size()
+ *   d_median_disparity [n_pairs]   vk::getMedian(disparities_): the element of rank floor(n / 2) in sorted order;
+ *                                  0 for a pair with no tracked point
+ * n_pts <= 1024 (SVO_HIP_ERANGE).
+ */
+int svo_hip_klt_summarize(const svo_hip_camera* cam, int n_pairs, int n_pts, const float* d_px_ref,
+                          const float* d_px_cur, const uint8_t* d_status, double* d_f_cur, double* d_disparity,
+                          int32_t* d_n_tracked, double* d_median_disparity, void* stream);
+
 /* static DepthFilter::computeTau(T_ref_cur, f, z, px_error_angle) (depth_filter.cpp:334-350) for S
  * independent measurements: d_t_ref_cur [S][3] = T_ref_cur.translation(), d_f [S][3], d_z [S].
  * Arithmetic (since round 5, here and inside svo_hip_update_seeds*): the ALGEBRAIC form -- alpha and beta enter only

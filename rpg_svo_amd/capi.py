@@ -106,6 +106,12 @@ class Reprojection(C.Structure):
                                           "d_trial_obs_begin", "d_trial_obs_end", "d_trial_cell", "d_trial_px")]
 
 
+class KltParams(C.Structure):
+    """svo_hip_klt_params: window, levels and stop rule of the pyramidal Lucas-Kanade tracker."""
+    _fields_ = [("win_size", C.c_int32), ("max_level", C.c_int32), ("max_iter", C.c_int32), ("eps", C.c_float),
+                ("min_eig_threshold", C.c_float)]
+
+
 REPROJ_MAX_IN_FRAME, REPROJ_MAX_CELLS, REPROJ_HEADER = 4096, 2048, 8
 FTR_CORNER, FTR_EDGELET = 0, 1
 SEED_ERASED_OLD, SEED_BEHIND, SEED_NOT_IN_FRAME, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = range(1, 8)
@@ -202,6 +208,9 @@ PROTOTYPES = {
     "svo_hip_update_seed_batch": (_i, [_i, _vp, _vp, C.POINTER(Seeds), _vp]),
     "svo_hip_fast_workspace_bytes": (C.c_size_t, [_LP, _i, _i]),
     "svo_hip_fast_detect": (_i, [_LP, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "svo_hip_klt_params_default": (_i, [C.POINTER(KltParams)]),
+    "svo_hip_klt_track": (_i, [_LP, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(KltParams), _vp]),
+    "svo_hip_klt_summarize": (_i, [C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svo_hip_compute_tau_batch": (_i, [_i, _vp, _vp, _vp, C.c_double, _vp, _vp]),
 }
 

@@ -1,0 +1,118 @@
+"""Batched host mirror of the tracking half of svo::initialization::KltHomographyInit (svo/src/initialization.cpp:29-54,
+107-169) over svo_hip_fast_detect, svo_hip_cam2world, svo_hip_klt_track and svo_hip_klt_summarize (K8).  Device-resident
+tensors only; n independent sequences bootstrap side by side.
+
+What is built ends where the reference calls computeHomography (:56): `add_frame` reports TRACKED for a sequence that has
+passed both gates, and f_ref / f_cur / status / disparities are what that call would be given.  The homography, the
+scale fix and the map (:56-98) are not part of this module.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import enum
+
+import torch
+
+from . import capi
+from .feature_detection import FastDetector
+from .pyramid import PyramidStore, _stream_ptr
+from .tracking import cam2world
+
+
+class InitResult(enum.IntEnum):
+    """initialization.h's InitResult, plus TRACKED: both gates of addSecondFrame passed, the homography step is next."""
+    FAILURE = 0
+    NO_KEYFRAME = 1
+    SUCCESS = 2
+    TRACKED = 3
+
+
+def klt_params() -> capi.KltParams:
+    p = capi.KltParams()
+    capi.check(capi.load().svo_hip_klt_params_default(C.byref(p)), "svo_hip_klt_params_default")
+    return p
+
+
+def klt_track(store: PyramidStore, ref_slot, cur_slot, px_ref, px_cur, status, error=None, params=None):
+    """svo_hip_klt_track on tensors: ref_slot / cur_slot [n] i32, px_ref [n, m, 2] f32, px_cur (in: initial flow, out)
+    and status [n, m] u8 are updated in place.  Returns error [n, m] f32."""
+    n, m = px_ref.shape[:2]
+    dev = store.device
+    for t, dt in ((ref_slot, torch.int32), (cur_slot, torch.int32), (px_ref, torch.float32), (px_cur, torch.float32), (status, torch.uint8)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous()
+    assert px_cur.shape == px_ref.shape and status.shape == (n, m) and ref_slot.shape == cur_slot.shape == (n,)
+    if error is None:
+        error = torch.zeros(n, m, dtype=torch.float32, device=dev)
+    params = params or klt_params()
+    capi.check(capi.load().svo_hip_klt_track(C.byref(store.layout), store.ptr, n, ref_slot.data_ptr(), cur_slot.data_ptr(), m,
+                                             px_ref.data_ptr(), px_cur.data_ptr(), status.data_ptr(), error.data_ptr(),
+                                             C.byref(params), _stream_ptr(dev)), "svo_hip_klt_track")
+    return error
+
+
+def klt_summarize(cam, px_ref, px_cur, status):
+    """svo_hip_klt_summarize: -> (f_cur [n, m, 3] f64, disparity [n, m] f64, n_tracked [n] i32, median [n] f64)"""
+    n, m = px_ref.shape[:2]
+    dev = px_ref.device
+    f_cur = torch.empty(n, m, 3, dtype=torch.float64, device=dev)
+    disparity = torch.empty(n, m, dtype=torch.float64, device=dev)
+    n_tracked = torch.empty(n, dtype=torch.int32, device=dev)
+    median = torch.empty(n, dtype=torch.float64, device=dev)
+    c = capi.camera(cam)
+    capi.check(capi.load().svo_hip_klt_summarize(C.byref(c), n, m, px_ref.data_ptr(), px_cur.data_ptr(), status.data_ptr(),
+                                                 f_cur.data_ptr(), disparity.data_ptr(), n_tracked.data_ptr(), median.data_ptr(),
+                                                 _stream_ptr(dev)), "svo_hip_klt_summarize")
+    return f_cur, disparity, n_tracked, median
+
+
+class KltTracker:
+    """KltHomographyInit up to computeHomography, for n sequences at once.  The defaults are the reference's Config
+    values (gridSize 30, nPyrLevels 3, initMinTracked 50, initMinDisparity 50, triangMinCornerScore 20)."""
+
+    MIN_FIRST_FRAME_CORNERS = 100   # initialization.cpp:33
+
+    def __init__(self, cam, grid_size: int = 30, n_pyr_levels: int = 3, min_tracked: int = 50, min_disparity: float = 50.0,
+                 min_corner_score: float = 20.0):
+        self.cam = cam
+        self.min_tracked = min_tracked
+        self.min_disparity = min_disparity
+        self.min_corner_score = min_corner_score
+        self.detector = FastDetector(cam.width, cam.height, grid_size, n_pyr_levels)
+        self.params = klt_params()
+        self.ref_slots = None
+
+    def add_first_frame(self, store: PyramidStore, slots: torch.Tensor) -> torch.Tensor:
+        """addFirstFrame (:29-41) -> [n] InitResult values (i32): SUCCESS, or FAILURE with fewer than 100 corners.
+        Sets px_ref [n, cells, 2] f32 (cell order, as detectFeatures fills px_vec), status (the validity mask: 1 where
+        the cell holds a corner), px_cur = px_ref, f_ref [n, cells, 3]."""
+        if store.n_levels <= self.params.max_level:
+            raise capi.SvoHipError(f"the tracker reads pyramid levels 0..{self.params.max_level}: the store has {store.n_levels}")
+        xy, _, score = self.detector.detect(store, slots, self.min_corner_score)
+        n, cells = score.shape
+        self.ref_slots = slots.clone()
+        self.status = (score > self.min_corner_score).to(torch.uint8).contiguous()
+        self.px_ref = xy.to(torch.float32).contiguous()            # cv::Point2f(ftr->px[0], ftr->px[1])
+        self.px_cur = self.px_ref.clone()
+        self.f_ref = cam2world(self.cam, xy.to(torch.float64).reshape(-1, 2)).reshape(n, cells, 3)
+        self.f_ref = self.f_ref * self.status[..., None].to(torch.float64)
+        self.f_cur = torch.zeros_like(self.f_ref)
+        self.disparities = torch.zeros(n, cells, dtype=torch.float64, device=store.device)
+        self.error = torch.zeros(n, cells, dtype=torch.float32, device=store.device)
+        self.n_tracked = self.status.sum(dim=1, dtype=torch.int32)
+        self.median_disparity = torch.zeros(n, dtype=torch.float64, device=store.device)
+        ok = self.n_tracked >= self.MIN_FIRST_FRAME_CORNERS
+        return torch.where(ok, int(InitResult.SUCCESS), int(InitResult.FAILURE)).to(torch.int32)
+
+    def add_frame(self, store: PyramidStore, slots: torch.Tensor) -> torch.Tensor:
+        """trackKlt and the gates of addSecondFrame (:45-54) -> [n] InitResult values: FAILURE (fewer than min_tracked
+        points left), NO_KEYFRAME (median disparity below min_disparity) or TRACKED.  px_cur and status carry over to
+        the next call like px_cur_ and the erased vectors."""
+        if self.ref_slots is None:
+            raise capi.SvoHipError("add_first_frame has not been called")
+        assert slots.dtype == torch.int32 and slots.shape == self.ref_slots.shape
+        klt_track(store, self.ref_slots, slots.contiguous(), self.px_ref, self.px_cur, self.status, self.error, self.params)
+        self.f_cur, self.disparities, self.n_tracked, self.median_disparity = klt_summarize(self.cam, self.px_ref, self.px_cur, self.status)
+        res = torch.full_like(self.n_tracked, int(InitResult.TRACKED))
+        res = torch.where(self.median_disparity < self.min_disparity, int(InitResult.NO_KEYFRAME), res)
+        res = torch.where(self.n_tracked < self.min_tracked, int(InitResult.FAILURE), res)
+        return res

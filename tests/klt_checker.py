@@ -1,0 +1,122 @@
+"""TEST INFRASTRUCTURE.  The specification of svo_hip_klt_track / svo_hip_klt_summarize (include/svo_hip.h) written straight
+down in numpy f64, one point at a time, no attempt at speed: Bouguet's pyramidal Lucas-Kanade with a W x W window, Scharr
+derivatives, bilinear sampling of a level continued by its border pixels, OpenCV's documented stop rules.  Shares no code
+with the kernels (rpg_svo_amd/csrc/klt_track.hip) and imports nothing of the package."""
+import numpy as np
+
+FLT_EPSILON = 1.1920929e-07
+
+
+def _fetch(img, xs, ys):
+    """img at the integer grid ys x xs, every coordinate clamped to the level (replicated border)."""
+    h, w = img.shape
+    return img[np.clip(ys, 0, h - 1)[:, None], np.clip(xs, 0, w - 1)[None, :]].astype(np.float64)
+
+
+def _bilinear(V, ax, ay):
+    """V on a (W + 1) x (W + 1) integer grid -> W x W samples at offset (ax, ay) from the grid"""
+    return (1 - ax) * (1 - ay) * V[:-1, :-1] + ax * (1 - ay) * V[:-1, 1:] + (1 - ax) * ay * V[1:, :-1] + ax * ay * V[1:, 1:]
+
+
+def _corner(t, size, W):
+    """floor(t) if the window's corner is within [-W, size) of the level, else None"""
+    f = np.floor(t)
+    if not (f >= -W and f < size):   # (also NaN / infinity)
+        return None
+    return int(f)
+
+
+def _window(img, tx, ty, W, derivatives):
+    """The W x W window whose pixel (i, j) is img sampled at (tx + j, ty + i); with derivatives also Ix, Iy: the
+    Scharr images (rows [3 10 3] / 32 against [-1 0 1]) of the continued level sampled at the same positions.
+    None when the corner fails the bounds test."""
+    h, w = img.shape
+    ix, iy = _corner(tx, w, W), _corner(ty, h, W)
+    if ix is None or iy is None:
+        return None
+    ax, ay = tx - ix, ty - iy
+    if not derivatives:
+        return _bilinear(_fetch(img, ix + np.arange(W + 1), iy + np.arange(W + 1)), ax, ay)
+    P = _fetch(img, ix + np.arange(-1, W + 2), iy + np.arange(-1, W + 2))   # one pixel more on every side
+    Sx = 3 * (P[:-2, 2:] - P[:-2, :-2]) + 10 * (P[1:-1, 2:] - P[1:-1, :-2]) + 3 * (P[2:, 2:] - P[2:, :-2])
+    Sy = 3 * (P[2:, :-2] - P[:-2, :-2]) + 10 * (P[2:, 1:-1] - P[:-2, 1:-1]) + 3 * (P[2:, 2:] - P[:-2, 2:])
+    return _bilinear(P[1:-1, 1:-1], ax, ay), _bilinear(Sx, ax, ay) / 32.0, _bilinear(Sy, ax, ay) / 32.0
+
+
+def track_point(pyr_ref, pyr_cur, p_ref, q_in, W=30, max_level=4, max_iter=30, eps=1e-3, min_eig_threshold=1e-4):
+    """One point.  Returns (px_cur [2], status, error, iterations per level [max_level + 1])."""
+    half = (W - 1) / 2.0
+    q = np.array(q_in, dtype=np.float64) / (1 << max_level)
+    iters = np.zeros(max_level + 1, dtype=np.int64)
+    error = 0.0
+    for l in range(max_level, -1, -1):
+        if l != max_level:
+            q = q * 2.0
+        p = np.array(p_ref, dtype=np.float64) / (1 << l)
+        ref, cur = pyr_ref[l], pyr_cur[l]
+        T = _window(ref, p[0] - half, p[1] - half, W, True)
+        if T is None:
+            if l == 0:
+                return q, 0, 0.0, iters
+            continue
+        I, Ix, Iy = T
+        a11, a12, a22 = (Ix * Ix).sum(), (Ix * Iy).sum(), (Iy * Iy).sum()
+        D = a11 * a22 - a12 * a12
+        min_eig = (a11 + a22 - np.sqrt((a11 - a22) ** 2 + 4 * a12 * a12)) / (2 * W * W)
+        if min_eig < min_eig_threshold or D < FLT_EPSILON:
+            if l == 0:
+                return q, 0, 0.0, iters
+            continue
+        prev = None
+        for it in range(max_iter):
+            J = _window(cur, q[0] - half, q[1] - half, W, False)
+            if J is None:
+                if l == 0:
+                    return q, 0, 0.0, iters
+                break
+            iters[l] += 1
+            diff = J - I
+            b1, b2 = (diff * Ix).sum(), (diff * Iy).sum()
+            delta = np.array([(a12 * b2 - a22 * b1) / D, (a12 * b1 - a11 * b2) / D])
+            q = q + delta
+            if delta @ delta <= eps * eps:
+                break
+            if it > 0 and abs(delta[0] + prev[0]) < 0.01 and abs(delta[1] + prev[1]) < 0.01:
+                q = q - delta * 0.5
+                break
+            prev = delta
+        if l == 0:
+            J = _window(cur, q[0] - half, q[1] - half, W, False)
+            if J is None:
+                return q, 0, 0.0, iters
+            error = np.abs(J - I).mean()
+    return q, 1, error, iters
+
+
+def track(pyr_ref, pyr_cur, px_ref, px_cur, status, **kw):
+    """svo_hip_klt_track for one pair.  px_ref, px_cur [n, 2] (taken as the f32 values the device is given), status [n]
+    in; returns (px_cur f64 [n, 2], status u8 [n], error f64 [n], iterations [n, levels]); points with status 0 on input
+    keep their px_cur, error is 0 for them."""
+    px_ref = np.asarray(px_ref, dtype=np.float32).astype(np.float64)
+    out = np.asarray(px_cur, dtype=np.float32).astype(np.float64).copy()
+    st = np.asarray(status, dtype=np.uint8).copy()
+    err = np.zeros(len(st))
+    iters = np.zeros((len(st), kw.get("max_level", 4) + 1), dtype=np.int64)
+    for i in range(len(st)):
+        if st[i]:
+            out[i], st[i], err[i], iters[i] = track_point(pyr_ref, pyr_cur, px_ref[i], out[i], **kw)
+    return out, st, err, iters
+
+
+def disparities(px_ref, px_cur):
+    """Vector2d(px_ref.x - px_cur.x, px_ref.y - px_cur.y).norm() of cv::Point2f: f32 differences, f64 norm"""
+    e = (np.asarray(px_ref, dtype=np.float32) - np.asarray(px_cur, dtype=np.float32)).astype(np.float64)
+    return np.sqrt(e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1])
+
+
+def summarize(px_ref, px_cur, status):
+    """(disparity [n] (0 where lost), n_tracked, vk::getMedian of the tracked points' disparities (0 when none))"""
+    on = np.asarray(status) != 0
+    d = np.where(on, disparities(px_ref, px_cur), 0.0)
+    n = int(on.sum())
+    return d, n, (sorted(d[on])[n // 2] if n else 0.0)
