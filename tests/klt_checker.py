@@ -43,6 +43,20 @@ def _window(img, tx, ty, W, derivatives):
     return _bilinear(P[1:-1, 1:-1], ax, ay), _bilinear(Sx, ax, ay) / 32.0, _bilinear(Sy, ax, ay) / 32.0
 
 
+def _structure(Ix, Iy, W):
+    """(a11, a12, a22, D, min_eig) of a template's derivatives"""
+    a11, a12, a22 = (Ix * Ix).sum(), (Ix * Iy).sum(), (Iy * Iy).sum()
+    return a11, a12, a22, a11 * a22 - a12 * a12, (a11 + a22 - np.sqrt((a11 - a22) ** 2 + 4 * a12 * a12)) / (2 * W * W)
+
+
+def template_min_eig(level_img, p, W=30):
+    """min_eig of the template at position p (pixels of that level) of one pyramid level: the number the
+    min_eig_threshold rule looks at.  NaN when the template fails the bounds test."""
+    half = (W - 1) / 2.0
+    T = _window(level_img, p[0] - half, p[1] - half, W, True)
+    return np.nan if T is None else _structure(T[1], T[2], W)[4]
+
+
 def track_point(pyr_ref, pyr_cur, p_ref, q_in, W=30, max_level=4, max_iter=30, eps=1e-3, min_eig_threshold=1e-4):
     """One point.  Returns (px_cur [2], status, error, iterations per level [max_level + 1])."""
     half = (W - 1) / 2.0
@@ -60,9 +74,7 @@ def track_point(pyr_ref, pyr_cur, p_ref, q_in, W=30, max_level=4, max_iter=30, e
                 return q, 0, 0.0, iters
             continue
         I, Ix, Iy = T
-        a11, a12, a22 = (Ix * Ix).sum(), (Ix * Iy).sum(), (Iy * Iy).sum()
-        D = a11 * a22 - a12 * a12
-        min_eig = (a11 + a22 - np.sqrt((a11 - a22) ** 2 + 4 * a12 * a12)) / (2 * W * W)
+        a11, a12, a22, D, min_eig = _structure(Ix, Iy, W)
         if min_eig < min_eig_threshold or D < FLT_EPSILON:
             if l == 0:
                 return q, 0, 0.0, iters

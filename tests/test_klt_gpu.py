@@ -19,24 +19,12 @@ import torch
 
 import klt_checker
 import klt_scenes
+from klt_edge_cases import compare_with_checker, PX_TOL
 from rpg_svo_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
 
-PX_TOL, ERR_TOL = 5e-3, 1e-2
 MED_TOL = 2 ** 0.5 * PX_TOL   # a disparity is the norm of a difference whose two coordinates each move by <= PX_TOL
-
-
-def compare_with_checker(name, px, st, err, ref, cap=0.01):
-    agree_st = st == ref["st"]
-    both = agree_st & (st != 0)
-    dpx = np.where(both, np.abs(px.astype(np.float64) - ref["px"]).max(axis=1), 0.0)
-    derr = np.where(both, np.abs(err.astype(np.float64) - ref["err"]), 0.0)
-    bad = ~agree_st | (dpx > PX_TOL) | (derr > ERR_TOL)
-    text = f"{name}: {int(bad.sum())} of {len(st)} points differ (status {int((~agree_st).sum())}), max |dpx| {dpx.max():.2e} px, max |derr| {derr.max():.2e}; " \
-           f"exceptions: {[(int(i), int(st[i]), int(ref['st'][i]), float(dpx[i])) for i in np.flatnonzero(bad)]}"
-    print(text)
-    assert bad.sum() <= cap * len(st), text
 
 
 def make_store(images, dev, n_levels=5):
