@@ -809,6 +809,124 @@ int svo_hip_klt_summarize(const svo_hip_camera* cam, int n_pairs, int n_pts, con
                           const float* d_px_cur, const uint8_t* d_status, double* d_f_cur, double* d_disparity,
                           int32_t* d_n_tracked, double* d_median_disparity, void* stream);
 
+/* ---- K9: two-view bootstrap, homography, pose and first map (initialization.cpp:56-98, 171-195) ----------- */
+/*
+ * What KltHomographyInit::addSecondFrame does after its two gates, for n_pairs pairs of n_pts points each: the robust
+ * homography, its decomposition into a pose, vk::computeInliers with its triangulation, the initMinInliers decision,
+ * the scale fix and the first map points.  Not OpenCV's or vikit's bits (neither RANSAC's draws nor its LM can be
+ * reproduced): this comment states the algorithm, tests/homography_checker.py restates it in numpy f64.  All of it is
+ * f64, separate roundings except inside the hypothesis scores.
+ *
+ * Inputs per pair (what svo_hip_klt_track / svo_hip_klt_summarize leave): d_f_ref, d_f_cur [n_pts][3] unit bearings,
+ * d_status [n_pts] u8, d_px_ref, d_px_cur [n_pts][2] f32, d_T_ref_w [12].  The tracked points (status != 0), in index
+ * order, have ranks 0 .. m - 1; uv = (f0 / f2, f1 / f2) (vk::project2d), x = (u, v, 1).  focal = |cam->fx|
+ * (errorMultiplier2), thr = reproj_thresh.
+ *
+ * 1. Hypotheses k = 0 .. n_hypotheses - 1, no adaptive stop.  fmix(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13;
+ *    h *= 0xc2b2ae35; h ^= h >> 16 (murmur3's 32-bit finaliser, u32 arithmetic).  Draw j = 0..3 of hypothesis k:
+ *    h = fmix(fmix(seed + 0x9e3779b9) ^ (4 k + j)), r = (h * (m - j)) >> 32 (the high word of the 64-bit product); then
+ *    for each earlier pick of this hypothesis, in ascending order: if r >= pick, r += 1.  Pick j is r.  (The pair's
+ *    index is not hashed.)  With p1..p4 / q1..q4 the x of the picks in the reference / current view, in draw order:
+ *    M = [p1 p2 p3] (columns), adj(M) has the rows p2 x p3, p3 x p1, p1 x p2, lambda = adj(M) p4, A = M diag(lambda);
+ *    N, mu, B likewise from q; H = B adj(A) = N diag(mu1 l2 l3, mu2 l1 l3, mu3 l1 l2) adj(M), divided by H[2][2].
+ *    Rejected: a non-finite entry of H, or one of |lambda_i|, |det M| = |(p1 x p2) . p3| below 1e-10 * (|p1|^2 + .. +
+ *    |p4|^2) (three of the four points collinear), or the same for q.
+ *    Score = number of ranks with focal^2 |uv_cur - project2d(H x_ref)|^2 < 2^2 (cv::findHomography's
+ *    ransacReprojThreshold as the reference passes it); a NaN does not count.  The winner has the largest score, ties
+ *    to the smallest k.  m < 4 or no accepted hypothesis: status NO_MODEL.
+ * 2. Refinement over the winner's inliers (the ranks its score counted; the set stays fixed): h = the eight entries
+ *    H[0][0] .. H[2][1], H[2][2] = 1; with (X, Y, W) = H x_ref, x = X / W, y = Y / W, residual r = uv_cur - (x, y),
+ *    cost = sum |r|^2, Jacobian rows of x: (u, v, 1, 0, 0, 0, -x u, -x v) / W, of y: (0, 0, 0, u, v, 1, -y u, -y v) / W.
+ *    Up to refine_iters times: solve (J'J) delta = J'r by an unpivoted LDL' (d_j = a_jj - sum_k l_jk^2 d_k,
+ *    l_ij = (a_ij - sum_k l_ik l_jk d_k) / d_j, forward, diagonal and backward substitution); a non-finite delta stops;
+ *    the cost at h + delta is formed, and the step is kept unless it raises the cost (or the cost is NaN), which stops.
+ *    Sums over ranks run in a fixed order (see below).
+ * 3. inlier_H[i] = focal^2 |uv_cur - project2d(H x_ref)|^2 < thr^2 with the refined H (computeMatchesInliers).
+ * 4. Decomposition (Faugeras-Lustman as PTAM / vikit have it).  H = U diag(d1 >= d2 >= d3) V', formed as: cyclic Jacobi
+ *    on H'H (10 sweeps over the pairs (0,1), (0,2), (1,2); a rotation with a zero off-diagonal entry is skipped),
+ *    eigenvalues sorted descending, d_i their square roots, each column v_i signed so that its entry of largest
+ *    magnitude (the first such) is positive, u_i = H v_i / d_i.  s = -1 if det U det V < 0, else 1.  Anything
+ *    non-finite, d1 - d2 < 1e-9 d2 or d2 - d3 < 1e-9 d2: status DEGENERATE.  (vikit tests d1 == d2 and d2 == d3 on
+ *    bits; two identical views give singular values that differ in their last bits, so the test is a relative one here.)
+ *    x1 = sqrt((d1^2 - d2^2) / (d1^2 - d3^2)), x3 = sqrt((d2^2 - d3^2) / (d1^2 - d3^2)).  Candidates c = 0..7:
+ *    (e1, e3) = (1,1), (-1,1), (1,-1), (-1,-1) for c & 3 = 0..3.
+ *      c < 4,  d = s d2:   sin = (d1 - d3) x1 x3 e1 e3 / d2, cos = (d1 x3^2 + d3 x1^2) / d2,
+ *                          R' = [cos 0 -sin; 0 1 0; sin 0 cos],  t' = (d1 - d3) (x1 e1, 0, -x3 e3)
+ *      c >= 4, d = -s d2:  sin = (d1 + d3) x1 x3 e1 e3 / d2, cos = (d3 x1^2 - d1 x3^2) / d2,
+ *                          R' = [cos 0 sin; 0 -1 0; sin 0 -cos], t' = (d1 + d3) (x1 e1, 0, x3 e3)
+ *    n = V (x1 e1, 0, x3 e3), R = s U R' V', t = U t'.
+ * 5. Choice (findBestDecomposition).  score1[c] = number of H-inliers with (H20 u + H21 v + H22) / d > 0 (x_ref); the
+ *    candidates sorted by descending score1 (stable: ties in candidate order), the first four kept; score2[c] = number
+ *    of H-inliers with (x_ref . n) / d > 0; the four sorted by descending score2 (stable), the first two kept.  If
+ *    score2[second] / score2[first] < 0.9 (a division of doubles; 0 / 0 does not pass) the first wins.  Otherwise
+ *    `ambiguous` is set and the smaller sum over ALL ranks of min(Sampson error, 4 (thr / focal)^2) wins, the first on
+ *    a tie, where E = [t]x R, e = x_cur' E x_ref, Sampson error = e^2 / ((E x_ref)_0^2 + (E x_ref)_1^2 + (E' x_cur)_0^2
+ *    + (E' x_cur)_1^2), and a NaN term counts as the clamp.  (vikit's text clamps at a pixel value and builds E
+ *    with the operands in an order that is not the essential matrix of (R, t); here the clamp is in unit-plane units
+ *    and E is the geometrically correct one.)  T_cur_from_ref = [R | t] of the winner.
+ * 6. vk::computeInliers.  Per rank: triangulateFeatureNonLin(R, t, f_cur, f_ref): f2 = R f_ref, a00 = f_cur . f_cur,
+ *    a10 = f_cur . f2, a01 = -a10, a11 = -f2 . f2, b = (t . f_cur, t . f2), det = a00 a11 - a01 a10,
+ *    l0 = (a11 b0 - a01 b1) / det, l1 = (a00 b1 - a10 b0) / det, xyz = (l0 f_cur + (t + l1 f2)) / 2.
+ *    e1 = focal |project2d(f_cur) - project2d(xyz)|, e2 = focal |project2d(f_ref) - project2d(R'(xyz - t))|; the rank
+ *    is an inlier when e1 <= thr and e2 <= thr (a NaN makes an outlier).  xyz_in_cur is written for inliers and is 0
+ *    for every other point.  n_inliers < min_inliers: result FAILURE (status stays OK).
+ * 7. depth_median = the element of rank floor(n_inliers / 2) among the inliers' xyz.z in ascending order (ties by
+ *    index), scale = map_scale / depth_median; T_cur_w = T_cur_from_ref * T_ref_w (matrix products) with, pos() being
+ *    -R't, translation = -R_cur_w (pos_ref + scale (pos_cur - pos_ref)); point_w = R_cur_w' (scale xyz - translation);
+ *    point_ok = inlier and isInFrame(int(px_cur), 10) and isInFrame(int(px_ref), 10) and xyz.z > 0.
+ *
+ * Fixed order of every sum over ranks: work-item t of 256 adds its ranks t, t + 256, .. in ascending order; the 64
+ * partial sums of a wave are added by wave_reduce.h's exchange tree; the four wave totals as ((w0 + w1) + w2) + w3.
+ * One workgroup per pair, no atomics on floating point: the same call gives the same bits, and so do identical pairs
+ * at different batch positions.
+ *
+ * Outputs (struct of device pointers, all required).  A point with status 0 has zero outputs.  A pair that stops at
+ * a step keeps zeros in every output of the later steps (best_hypothesis is -1 for NO_MODEL); result is
+ * SVO_HIP_INIT_SUCCESS only when every step passed.
+ * Limits: n_pts <= 1024 and 1 <= n_hypotheses <= 4096 (SVO_HIP_ERANGE); refine_iters >= 0, min_inliers >= 0,
+ * reproj_thresh > 0, a known camera model, non-null pointers (SVO_HIP_EINVAL); n_pairs * n_pts == 0 is a successful
+ * no-op.  No allocation, no host read: the call can be captured into a HIP graph and replayed.
+ */
+#define SVO_HIP_INIT_FAILURE 0      /* initialization.h's InitResult */
+#define SVO_HIP_INIT_NO_KEYFRAME 1
+#define SVO_HIP_INIT_SUCCESS 2
+#define SVO_HIP_HOMOGRAPHY_OK 0
+#define SVO_HIP_HOMOGRAPHY_NO_MODEL 1
+#define SVO_HIP_HOMOGRAPHY_DEGENERATE 2
+typedef struct svo_hip_homography_params {
+  double reproj_thresh;  /* Config::poseOptimThresh(), 2.0 */
+  double map_scale;      /* Config::mapScale(), 1.0        */
+  int32_t min_inliers;   /* Config::initMinInliers(), 40   */
+  int32_t n_hypotheses;  /* 512                            */
+  int32_t refine_iters;  /* 10                             */
+  uint32_t seed;         /* 0                              */
+} svo_hip_homography_params;
+typedef struct svo_hip_homography_out {
+  double* d_H;                /* [n_pairs][9] row-major, H[2][2] = 1                  */
+  int32_t* d_best_hypothesis; /* [n_pairs]                                            */
+  int32_t* d_n_inliers_H;     /* [n_pairs]                                            */
+  uint8_t* d_inlier_H;        /* [n_pairs][n_pts]                                     */
+  double* d_T_cur_from_ref;   /* [n_pairs][12]                                        */
+  int32_t* d_ambiguous;       /* [n_pairs] 0 / 1                                      */
+  int32_t* d_status;          /* [n_pairs] SVO_HIP_HOMOGRAPHY_*                       */
+  double* d_xyz_in_cur;       /* [n_pairs][n_pts][3]                                  */
+  uint8_t* d_inlier;          /* [n_pairs][n_pts]                                     */
+  int32_t* d_n_inliers;       /* [n_pairs]                                            */
+  double* d_depth_median;     /* [n_pairs]                                            */
+  double* d_scale;            /* [n_pairs]                                            */
+  double* d_T_cur_w;          /* [n_pairs][12]                                        */
+  double* d_point_w;          /* [n_pairs][n_pts][3]                                  */
+  uint8_t* d_point_ok;        /* [n_pairs][n_pts]                                     */
+  int32_t* d_result;          /* [n_pairs] SVO_HIP_INIT_FAILURE / SVO_HIP_INIT_SUCCESS */
+} svo_hip_homography_out;
+/* host-only: (2.0, 1.0, 40, 512, 10, 0) */
+int svo_hip_homography_params_default(svo_hip_homography_params* out);
+int svo_hip_homography_init(const svo_hip_camera* cam, int n_pairs, int n_pts, const double* d_f_ref,
+                            const double* d_f_cur, const uint8_t* d_status, const float* d_px_ref,
+                            const float* d_px_cur, const double* d_T_ref_w,
+                            const svo_hip_homography_params* params, const svo_hip_homography_out* out,
+                            void* stream);
+
 /* static DepthFilter::computeTau(T_ref_cur, f, z, px_error_angle) (depth_filter.cpp:334-350) for S
  * independent measurements: d_t_ref_cur [S][3] = T_ref_cur.translation(), d_f [S][3], d_z [S].
  * Arithmetic (since round 5, here and inside svo_hip_update_seeds*): the ALGEBRAIC form -- alpha and beta enter only

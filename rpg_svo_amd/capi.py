@@ -112,6 +112,25 @@ class KltParams(C.Structure):
                 ("min_eig_threshold", C.c_float)]
 
 
+class HomographyParams(C.Structure):
+    """svo_hip_homography_params: thresholds of the bootstrap's homography step and this library's sampling parameters."""
+    _fields_ = [("reproj_thresh", C.c_double), ("map_scale", C.c_double), ("min_inliers", C.c_int32), ("n_hypotheses", C.c_int32),
+                ("refine_iters", C.c_int32), ("seed", C.c_uint32)]
+
+
+HOMOGRAPHY_OUTPUTS = ("H", "best_hypothesis", "n_inliers_H", "inlier_H", "T_cur_from_ref", "ambiguous", "status", "xyz_in_cur",
+                      "inlier", "n_inliers", "depth_median", "scale", "T_cur_w", "point_w", "point_ok", "result")
+
+
+class HomographyOut(C.Structure):
+    """svo_hip_homography_out: outputs of svo_hip_homography_init (device pointers)."""
+    _fields_ = [("d_" + n, C.c_void_p) for n in HOMOGRAPHY_OUTPUTS]
+
+
+INIT_FAILURE, INIT_NO_KEYFRAME, INIT_SUCCESS = 0, 1, 2
+HOMOGRAPHY_OK, HOMOGRAPHY_NO_MODEL, HOMOGRAPHY_DEGENERATE = 0, 1, 2
+HOMOGRAPHY_MAX_PTS, HOMOGRAPHY_MAX_HYPOTHESES = 1024, 4096
+
 REPROJ_MAX_IN_FRAME, REPROJ_MAX_CELLS, REPROJ_HEADER = 4096, 2048, 8
 FTR_CORNER, FTR_EDGELET = 0, 1
 SEED_ERASED_OLD, SEED_BEHIND, SEED_NOT_IN_FRAME, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = range(1, 8)
@@ -211,6 +230,9 @@ PROTOTYPES = {
     "svo_hip_klt_params_default": (_i, [C.POINTER(KltParams)]),
     "svo_hip_klt_track": (_i, [_LP, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(KltParams), _vp]),
     "svo_hip_klt_summarize": (_i, [C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svo_hip_homography_params_default": (_i, [C.POINTER(HomographyParams)]),
+    "svo_hip_homography_init": (_i, [C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(HomographyParams),
+                                     C.POINTER(HomographyOut), _vp]),
     "svo_hip_compute_tau_batch": (_i, [_i, _vp, _vp, _vp, C.c_double, _vp, _vp]),
 }
 

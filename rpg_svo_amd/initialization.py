@@ -1,10 +1,11 @@
-"""Batched host mirror of the tracking half of svo::initialization::KltHomographyInit (svo/src/initialization.cpp:29-54,
-107-169) over svo_hip_fast_detect, svo_hip_cam2world, svo_hip_klt_track and svo_hip_klt_summarize (K8).  Device-resident
+"""Batched host mirror of svo::initialization::KltHomographyInit (svo/src/initialization.cpp) over svo_hip_fast_detect,
+svo_hip_cam2world, svo_hip_klt_track, svo_hip_klt_summarize (K8) and svo_hip_homography_init (K9).  Device-resident
 tensors only; n independent sequences bootstrap side by side.
 
-What is built ends where the reference calls computeHomography (:56): `add_frame` reports TRACKED for a sequence that has
-passed both gates, and f_ref / f_cur / status / disparities are what that call would be given.  The homography, the
-scale fix and the map (:56-98) are not part of this module.
+KltTracker is the tracking half (:29-54, 107-169): `add_frame` reports TRACKED for a sequence that has passed both gates
+of addSecondFrame, and f_ref / f_cur / status / disparities are what computeHomography (:56) is given.
+KltHomographyInit adds the rest (:56-98, 171-195): the robust homography, its decomposition, computeInliers, the
+initMinInliers decision, the scale fix and the first map points, as include/svo_hip.h states them.
 """
 from __future__ import annotations
 
@@ -65,6 +66,50 @@ def klt_summarize(cam, px_ref, px_cur, status):
     return f_cur, disparity, n_tracked, median
 
 
+def homography_params(**kw) -> capi.HomographyParams:
+    p = capi.HomographyParams()
+    capi.check(capi.load().svo_hip_homography_params_default(C.byref(p)), "svo_hip_homography_params_default")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise capi.SvoHipError(f"svo_hip_homography_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+_HOMOGRAPHY_DTYPES = dict(H=torch.float64, best_hypothesis=torch.int32, n_inliers_H=torch.int32, inlier_H=torch.uint8,
+                          T_cur_from_ref=torch.float64, ambiguous=torch.int32, status=torch.int32, xyz_in_cur=torch.float64,
+                          inlier=torch.uint8, n_inliers=torch.int32, depth_median=torch.float64, scale=torch.float64,
+                          T_cur_w=torch.float64, point_w=torch.float64, point_ok=torch.uint8, result=torch.int32)
+
+
+def homography_outputs(n: int, m: int, device) -> dict:
+    """The tensors of svo_hip_homography_out for n pairs of m points, by field name (without the d_ prefix).  Allocate
+    once and hand them to every homography_init call that is captured into a HIP graph."""
+    shape = dict(H=(n, 9), T_cur_from_ref=(n, 12), T_cur_w=(n, 12), xyz_in_cur=(n, m, 3), point_w=(n, m, 3), inlier_H=(n, m),
+                 inlier=(n, m), point_ok=(n, m))
+    return {k: torch.zeros(shape.get(k, (n,)), dtype=dt, device=device) for k, dt in _HOMOGRAPHY_DTYPES.items()}
+
+
+def homography_init(cam, f_ref, f_cur, status, px_ref, px_cur, T_ref_w, params=None, out=None) -> dict:
+    """svo_hip_homography_init on tensors: f_ref / f_cur [n, m, 3] f64, status [n, m] u8, px_ref / px_cur [n, m, 2] f32,
+    T_ref_w [n, 12] f64 -> dict of the outputs (homography_outputs).  Enqueued on the current stream, not synchronised."""
+    n, m = status.shape
+    for t, dt, shape in ((f_ref, torch.float64, (n, m, 3)), (f_cur, torch.float64, (n, m, 3)), (status, torch.uint8, (n, m)),
+                         (px_ref, torch.float32, (n, m, 2)), (px_cur, torch.float32, (n, m, 2)), (T_ref_w, torch.float64, (n, 12))):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape
+    dev = status.device
+    out = homography_outputs(n, m, dev) if out is None else out
+    for k, dt in _HOMOGRAPHY_DTYPES.items():
+        assert out[k].dtype == dt and out[k].is_contiguous() and out[k].device == dev
+    o = capi.HomographyOut(*[out[k].data_ptr() for k in capi.HOMOGRAPHY_OUTPUTS])
+    c = capi.camera(cam)
+    params = params or homography_params()
+    capi.check(capi.load().svo_hip_homography_init(C.byref(c), n, m, f_ref.data_ptr(), f_cur.data_ptr(), status.data_ptr(),
+                                                   px_ref.data_ptr(), px_cur.data_ptr(), T_ref_w.data_ptr(), C.byref(params),
+                                                   C.byref(o), _stream_ptr(dev)), "svo_hip_homography_init")
+    return out
+
+
 class KltTracker:
     """KltHomographyInit up to computeHomography, for n sequences at once.  The defaults are the reference's Config
     values (gridSize 30, nPyrLevels 3, initMinTracked 50, initMinDisparity 50, triangMinCornerScore 20)."""
@@ -116,3 +161,52 @@ class KltTracker:
         res = torch.where(self.median_disparity < self.min_disparity, int(InitResult.NO_KEYFRAME), res)
         res = torch.where(self.n_tracked < self.min_tracked, int(InitResult.FAILURE), res)
         return res
+
+
+class KltHomographyInit(KltTracker):
+    """KltHomographyInit for n sequences at once: KltTracker's addFirstFrame and gates, then svo_hip_homography_init for
+    every sequence.  `homography` takes fields of svo_hip_homography_params (reproj_thresh = poseOptimThresh,
+    min_inliers = initMinInliers, map_scale = mapScale, n_hypotheses, refine_iters, seed)."""
+
+    def __init__(self, cam, homography: dict | None = None, **tracker):
+        super().__init__(cam, **tracker)
+        self.homography_params = homography_params(**(homography or {}))
+        self.T_ref_w = None
+        self.out = None
+
+    def add_first_frame(self, store: PyramidStore, slots: torch.Tensor, T_ref_w: torch.Tensor | None = None) -> torch.Tensor:
+        """addFirstFrame; T_ref_w [n, 12] f64 is frame_ref_->T_f_w_ (identity when omitted)."""
+        res = super().add_first_frame(store, slots)
+        n = slots.shape[0]
+        if T_ref_w is None:
+            T_ref_w = torch.tensor([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=torch.float64, device=store.device).repeat(n, 1)
+        assert T_ref_w.dtype == torch.float64 and tuple(T_ref_w.shape) == (n, 12)
+        self.T_ref_w = T_ref_w.contiguous()
+        self.out = None
+        return res
+
+    def add_second_frame(self, store: PyramidStore, slots: torch.Tensor) -> torch.Tensor:
+        """addSecondFrame (:43-99) -> [n] InitResult values: FAILURE (too few tracked points, no homography, or too few
+        inliers), NO_KEYFRAME (median disparity below min_disparity) or SUCCESS.  Sequences that do not pass the gates
+        enter the homography step with every point lost, so their outputs are the entry's zeros."""
+        gate = self.add_frame(store, slots)
+        tracked = gate == int(InitResult.TRACKED)
+        status = (self.status * tracked[:, None].to(torch.uint8)).contiguous()
+        n, m = status.shape
+        if self.out is None or self.out["inlier"].shape != (n, m):
+            self.out = homography_outputs(n, m, store.device)
+        homography_init(self.cam, self.f_ref, self.f_cur, status, self.px_ref, self.px_cur, self.T_ref_w, self.homography_params, self.out)
+        return torch.where(tracked, self.out["result"], gate)
+
+    # what the reference's members hold after addSecondFrame, for every sequence
+    T_cur_from_ref = property(lambda self: self.out["T_cur_from_ref"])   # [n, 12]
+    T_f_w = property(lambda self: self.out["T_cur_w"])                   # frame_cur->T_f_w_ [n, 12]
+    inliers = property(lambda self: self.out["inlier"])                  # [n, cells] u8 mask (inliers_ as indices in the reference)
+    n_inliers = property(lambda self: self.out["n_inliers"])
+    xyz_in_cur = property(lambda self: self.out["xyz_in_cur"])           # [n, cells, 3], 0 where not an inlier
+    points = property(lambda self: self.out["point_w"])                  # [n, cells, 3] Point::pos_ of the new map points
+    point_ok = property(lambda self: self.out["point_ok"])               # [n, cells] u8: the inliers that become map points
+    scale = property(lambda self: self.out["scale"])
+    ambiguous = property(lambda self: self.out["ambiguous"])
+    H = property(lambda self: self.out["H"])
+    homography_status = property(lambda self: self.out["status"])

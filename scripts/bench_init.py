@@ -1,0 +1,159 @@
+#!/usr/bin/env python
+"""Times the bootstrap's homography step (svo_hip_homography_init, csrc/homography_init.hip) on synthetic two-view scenes
+resident in HBM (tests/homography_cases.py: a plane with 3 % relief, 0.3 px noise, 30 % outliers, 352 tracked points) and
+writes profiles/homography_bench.json:
+
+  (a) one pair x 352 points    a single camera's bootstrap frame: one workgroup, launch- and latency-bound
+  (b) 4096 pairs x 352 points  the replay shape, beside klt_track's 33.8 ms for the same batch (profiles/klt_bench.json)
+
+Call times are device events around one call after a warm-up, median of 10; the kernel time of (b) comes from a
+`rocprofv3 --kernel-trace --stats` run of its own (this script started again with --traced-child); registers / scratch /
+occupancy from the compiler's resource-usage remarks.  The algorithmic f64 operation count is derived from the shapes
+(operations() below) and the kernel is placed against operations / peak vector f64 rate.  Needs an MI355X: there is no
+CPU path, and nothing is measured without one (the JSON then says "not measured")."""
+from __future__ import annotations
+
+import argparse
+import csv
+import glob
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+PEAK_F64_OPS = 78.6e12    # vector f64, an FMA counted as two (MI355X specification)
+KLT_TRACK_MS = 33.8       # svo_hip_klt_track, 4096 pairs x 352 points (profiles/klt_bench.json)
+POINTS, DISTINCT = 352, 64
+KERNEL = "homography_init_kernel"
+
+
+def operations(m, n_hypotheses, refine_iters, inlier_share=0.7):
+    """f64 operations one pair needs, a multiply, an add, a compare and a division each counted as one.
+    Hypothesis: two projective bases (3 cross products 27, |p|^2 sum 20, determinant 5, lambda 15: 67 each), the three
+    column factors 6, B adj(A) 54, nine divisions: 203.  Score per point: H x 12, reciprocal 1, projection and
+    differences 4, squared norm 3, compare 1: 21.  Refinement per evaluation and inlier: H x 12, five divisions, residual
+    2, the 30 products and sums 74: 93; an 8 x 8 LDL' with its substitutions about 400.  The inlier pass, the candidate
+    scores (8 candidates x 7), triangulation (about 90) and the map points (about 40) are per point, once."""
+    hyp = n_hypotheses * (203 + 21 * m)
+    refine = (refine_iters + 1) * (93 * inlier_share * m) + refine_iters * 400
+    rest = m * (21 + 56 + 90 + 40)
+    return hyp + refine + rest
+
+
+def compiler_resources():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    with tempfile.TemporaryDirectory() as tmp:
+        from rpg_svo_amd.build import FLAGS
+        r = subprocess.run([hipcc, *FLAGS, "-c", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rpg_svo_amd", "csrc"),
+                            os.path.join(ROOT, "rpg_svo_amd", "csrc", "homography_init.hip"), "-o", os.path.join(tmp, "hi.o"),
+                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    for blk in r.stderr.split("Function Name: ")[1:]:
+        if KERNEL in blk.split()[0]:
+            g = lambda key: int(re.search(key + r": (\d+)", blk).group(1))
+            return {"vgprs": g("VGPRs"), "agprs": g("AGPRs"), "sgprs": g("TotalSGPRs"), "scratch_bytes_per_lane": g(r"ScratchSize \[bytes/lane\]"),
+                    "occupancy_waves_per_simd": g(r"Occupancy \[waves/SIMD\]"), "lds_bytes_per_block": g(r"LDS Size \[bytes/block\]")}
+    return "not measured"
+
+
+def make_inputs(dev, n_pairs):
+    """n_pairs pairs of 352 tracked points: DISTINCT scenes, repeated"""
+    import numpy as np
+    import torch
+    import homography_cases as cases
+    pairs = [cases.make_pair(5000 + k, POINTS, n_lost=0) for k in range(min(DISTINCT, n_pairs))]
+    b = cases._batch("bench", pairs)
+    reps = -(-n_pairs // len(pairs))
+    inp = {k: torch.from_numpy(np.tile(v, (reps,) + (1,) * (v.ndim - 1))[:n_pairs].copy()).to(dev) for k, v in cases.inputs(b).items()}
+    return b.cam, inp
+
+
+def time_shape(dev, n_pairs, steps, warmup):
+    import torch
+    from rpg_svo_amd import initialization as init
+    cam, inp = make_inputs(dev, n_pairs)
+    out = init.homography_outputs(n_pairs, POINTS, dev)
+    params = init.homography_params()
+    times = []
+    for i in range(warmup + steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        init.homography_init(cam, inp["f_ref"], inp["f_cur"], inp["status"], inp["px_ref"], inp["px_cur"], inp["T_ref_w"], params, out)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            times.append(e0.elapsed_time(e1))
+    times.sort()
+    med = times[len(times) // 2]
+    ops = operations(POINTS, params.n_hypotheses, params.refine_iters)
+    return {"pairs": n_pairs, "points": POINTS, "n_hypotheses": int(params.n_hypotheses), "refine_iters": int(params.refine_iters), "steps": steps,
+            "call_ms_median": med, "call_ms_min": times[0], "call_ms_max": times[-1], "pairs_per_s": n_pairs / (med * 1e-3),
+            "success_fraction": float((out["result"] == 2).float().mean().item()),
+            "ambiguous_fraction": float(out["ambiguous"].float().mean().item()),
+            "mean_inliers": float(out["n_inliers"].float().mean().item()), "f64_ops_per_pair": ops}
+
+
+def traced_kernel_ms(args):
+    """Kernel time of shape (b) from rocprofv3's kernel trace, in a run of its own."""
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    out = tempfile.mkdtemp(prefix="init_trace_", dir=os.path.join(ROOT, "build"))
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "trace", "--", sys.executable,
+           os.path.abspath(__file__), "--traced-child", "--pairs", str(args.pairs)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    files = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
+    if r.returncode != 0 or not files:
+        return {"error": f"rocprofv3 exit {r.returncode}: {r.stderr[-400:]}"}
+    for row in csv.DictReader(open(files[0])):
+        if KERNEL in row.get("Name", ""):
+            return {"calls": int(row["Calls"]), "average_ms": float(row["AverageNs"]) * 1e-6, "min_ms": float(row["MinNs"]) * 1e-6,
+                    "max_ms": float(row["MaxNs"]) * 1e-6}
+    return {"error": "the kernel is not in the trace"}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--pairs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--no-compiler", action="store_true", help="skip the compile that reports registers, scratch and occupancy")
+    ap.add_argument("--traced-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "homography_bench.json"))
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        res = {"device": "not measured", "single_pair": "not measured", "replay_batch": "not measured", "rocprofv3": "not measured",
+               "compiler": "not measured" if args.no_compiler else compiler_resources(),
+               "f64_ops_per_pair": operations(POINTS, 512, 10), "note": "no MI355X was available: nothing here is measured without one"}
+    else:
+        dev = torch.device("cuda:0")
+        if args.traced_child:
+            time_shape(dev, args.pairs, 3, 1)
+            return
+        res = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("SVO_HIP_LIB", "in-tree")}
+        res["single_pair"] = time_shape(dev, 1, max(args.steps, 10), 5)
+        res["single_pair"]["note"] = "one workgroup on one CU: launch- and latency-bound"
+        res["replay_batch"] = time_shape(dev, args.pairs, args.steps, args.warmup)
+        res["compiler"] = "not measured" if args.no_compiler else compiler_resources()
+        res["rocprofv3"] = "not measured" if args.no_trace else traced_kernel_ms(args)
+        kern = res["rocprofv3"].get("average_ms") if isinstance(res["rocprofv3"], dict) else None
+        t_ms = kern if kern else res["replay_batch"]["call_ms_median"]
+        ops = res["replay_batch"]["f64_ops_per_pair"] * args.pairs
+        res["f64_bound"] = {"time_basis": "rocprofv3 kernel time" if kern else "device events", "time_ms": t_ms, "f64_ops": ops,
+                            "peak_f64_ops_per_s": PEAK_F64_OPS, "least_ms_by_operations": ops / PEAK_F64_OPS * 1e3,
+                            "achieved_f64_ops_per_s": ops / (t_ms * 1e-3), "share_of_bound": ops / PEAK_F64_OPS * 1e3 / t_ms,
+                            "klt_track_ms_same_batch": KLT_TRACK_MS, "share_of_klt_track": t_ms / KLT_TRACK_MS}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
