@@ -21,6 +21,10 @@
 //
 // List surgery (erasing seeds, creating svo::Point objects, the converged callback) stays on
 // the host: the kernel reports a status per seed and the new point's position.
+//
+// Entry points: svo_hip_update_seeds, svo_hip_update_seeds_resident[_pose] and svo_hip_find_epipolar_match_direct share
+// seed_args_begin (the common checks and fields of SeedArgs), add the pointers and fields that are their own and call
+// run_seed_chain.
 #pragma clang fp contract(off)
 #include <atomic>
 
@@ -384,6 +388,36 @@ static int run_seed_chain(const svo_hip_pyr_layout* layout, const uint8_t* d_sto
                           size_t workspace_bytes, hipStream_t st);
 static std::atomic<bool> g_count_evaluations{false};  // svo_hip_update_seeds_count_evaluations
 
+// What the four seed entries share: their checks, in the order that decides a return code -- struct pointers and S (EINVAL),
+// the empty batch (returns 1: the entry answers OK), the tables behind frames / ftr / seeds and the options (EINVAL) -- and
+// the fields of the entry's value-initialised `a` that do not depend on the entry.  The match-only entry has no seed state
+// (seeds == NULL).  An entry goes on with the pointers only it needs (EINVAL), the workspace (ERANGE, after every EINVAL) and
+// its own fields; what it does not set stays zero.
+static int seed_args_begin(SeedArgs& a, const svo_hip_pyr_layout* layout, const uint8_t* d_store, const svo_hip_camera* cam,
+                           const svo_hip_frames* frames, int S, const svo_hip_features* ftr, const svo_hip_seeds* seeds,
+                           bool match_only, const svo_hip_depth_filter_options* opt) {
+  if (!layout_ok(layout) || !d_store || !cam || !cam_model_ok(cam) || !frames || !ftr || (!match_only && !seeds) || !opt || S < 0)
+    return SVO_HIP_EINVAL;
+  if (S == 0) return 1;
+  if (!frames->d_slot || !frames->d_T_f_w || !ftr->d_frame || !ftr->d_level || !ftr->d_px || !ftr->d_f) return SVO_HIP_EINVAL;
+  if (!match_only && (!seeds->d_a || !seeds->d_b || !seeds->d_mu || !seeds->d_z_range || !seeds->d_sigma2 || !seeds->d_batch_id))
+    return SVO_HIP_EINVAL;
+  if (ftr->d_type && !ftr->d_grad) return SVO_HIP_EINVAL;
+  if (opt->n_pyr_levels < 1 || opt->n_pyr_levels > layout->n_levels || opt->align_max_iter < 0 || opt->max_epi_search_steps < 0)
+    return SVO_HIP_EINVAL;
+  a.L = *layout;
+  a.store = d_store;
+  a.cam = make_cam(cam);
+  a.S = S;
+  a.frame_slot = frames->d_slot;
+  a.frame_T = frames->d_T_f_w;
+  a.ftr = *ftr;
+  if (!match_only) a.seeds = *seeds;
+  a.opt = *opt;
+  a.match_only = match_only;
+  return SVO_HIP_OK;
+}
+
 extern "C" int svo_hip_find_epipolar_match_direct(const svo_hip_pyr_layout* layout, const uint8_t* d_store,
                                                   const svo_hip_camera* cam, const svo_hip_frames* frames, int S,
                                                   const int32_t* d_cur_frame, const svo_hip_features* ftr,
@@ -391,35 +425,13 @@ extern "C" int svo_hip_find_epipolar_match_direct(const svo_hip_pyr_layout* layo
                                                   const svo_hip_depth_filter_options* opt, int32_t* d_ok, double* d_depth,
                                                   double* d_px_cur, int32_t* d_search_level, void* d_workspace,
                                                   size_t workspace_bytes, void* stream) {
-  if (!layout_ok(layout) || !d_store || !cam || !cam_model_ok(cam) || !frames || !ftr || !opt || S < 0) return SVO_HIP_EINVAL;
-  if (S == 0) return SVO_HIP_OK;
-  if (!d_cur_frame || !d_ok || !d_depth || !d_d_estimate || !d_d_min || !d_d_max || !frames->d_slot || !frames->d_T_f_w ||
-      !ftr->d_frame || !ftr->d_level || !ftr->d_px || !ftr->d_f)
-    return SVO_HIP_EINVAL;
-  if (ftr->d_type && !ftr->d_grad) return SVO_HIP_EINVAL;
-  if (opt->n_pyr_levels < 1 || opt->n_pyr_levels > layout->n_levels || opt->align_max_iter < 0 || opt->max_epi_search_steps < 0)
-    return SVO_HIP_EINVAL;
+  SeedArgs a{};
+  const int rc = seed_args_begin(a, layout, d_store, cam, frames, S, ftr, nullptr, true, opt);
+  if (rc != SVO_HIP_OK) return rc > 0 ? SVO_HIP_OK : rc;
+  if (!d_cur_frame || !d_ok || !d_depth || !d_d_estimate || !d_d_min || !d_d_max) return SVO_HIP_EINVAL;
   if (!d_workspace || workspace_bytes < svo_hip_match_workspace_bytes(S)) return SVO_HIP_ERANGE;
-  SeedArgs a;
-  a.L = *layout;
-  a.store = d_store;
-  a.cam = make_cam(cam);
-  a.S = S;
-  a.frame_slot = frames->d_slot;
-  a.frame_T = frames->d_T_f_w;
   a.cur_frame = d_cur_frame;
-  a.cur_index = 0;
-  a.cur_T_set = 0;
-  a.slot_of = nullptr;
-  a.state_out = nullptr;
-  a.ftr = *ftr;
-  a.seeds.d_a = a.seeds.d_b = a.seeds.d_mu = a.seeds.d_z_range = a.seeds.d_sigma2 = nullptr;
-  a.seeds.d_batch_id = nullptr;
-  a.opt = *opt;
-  a.status_out = nullptr;
-  a.xyz_world = nullptr;
   a.px_cur_out = d_px_cur;
-  a.match_only = 1;
   a.d_est = d_d_estimate;
   a.d_min = d_d_min;
   a.d_max = d_d_max;
@@ -435,40 +447,15 @@ extern "C" int svo_hip_update_seeds(const svo_hip_pyr_layout* layout, const uint
                                     const svo_hip_seeds* seeds, const svo_hip_depth_filter_options* opt,
                                     int32_t* d_status, double* d_xyz_world, double* d_px_cur, void* d_workspace,
                                     size_t workspace_bytes, void* stream) {
-  if (!layout_ok(layout) || !d_store || !cam || !cam_model_ok(cam) || !frames || !ftr || !seeds || !opt || S < 0) return SVO_HIP_EINVAL;
-  if (S == 0) return SVO_HIP_OK;
-  if (!d_cur_frame || !d_status || !frames->d_slot || !frames->d_T_f_w || !ftr->d_frame || !ftr->d_level ||
-      !ftr->d_px || !ftr->d_f || !seeds->d_a || !seeds->d_b || !seeds->d_mu || !seeds->d_z_range ||
-      !seeds->d_sigma2 || !seeds->d_batch_id)
-    return SVO_HIP_EINVAL;
-  if (ftr->d_type && !ftr->d_grad) return SVO_HIP_EINVAL;
-  if (opt->n_pyr_levels < 1 || opt->n_pyr_levels > layout->n_levels || opt->align_max_iter < 0 ||
-      opt->max_epi_search_steps < 0)
-    return SVO_HIP_EINVAL;
+  SeedArgs a{};
+  const int rc = seed_args_begin(a, layout, d_store, cam, frames, S, ftr, seeds, false, opt);
+  if (rc != SVO_HIP_OK) return rc > 0 ? SVO_HIP_OK : rc;
+  if (!d_cur_frame || !d_status) return SVO_HIP_EINVAL;
   if (!d_workspace || workspace_bytes < svo_hip_match_workspace_bytes(S)) return SVO_HIP_ERANGE;
-  SeedArgs a;
-  a.L = *layout;
-  a.store = d_store;
-  a.cam = make_cam(cam);
-  a.S = S;
-  a.frame_slot = frames->d_slot;
-  a.frame_T = frames->d_T_f_w;
   a.cur_frame = d_cur_frame;
-  a.cur_index = 0;
-  a.cur_T_set = 0;
-  a.slot_of = nullptr;
-  a.state_out = nullptr;
-  a.ftr = *ftr;
-  a.seeds = *seeds;
-  a.opt = *opt;
   a.status_out = d_status;
   a.xyz_world = d_xyz_world;
   a.px_cur_out = d_px_cur;
-  a.match_only = 0;
-  a.d_est = a.d_min = a.d_max = nullptr;
-  a.depth_out = nullptr;
-  a.ok_out = nullptr;
-  a.search_level_out = nullptr;
   return run_seed_chain(layout, d_store, a, S, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
@@ -530,41 +517,21 @@ static int update_seeds_resident_impl(const svo_hip_pyr_layout* layout, const ui
                                       const svo_hip_seeds* seeds, const svo_hip_depth_filter_options* opt,
                                       int32_t* d_status, double* d_xyz_world, double* d_px_cur, float* d_state_out,
                                       void* d_workspace, size_t workspace_bytes, void* stream) {
-  if (!layout_ok(layout) || !d_store || !cam || !cam_model_ok(cam) || !frames || !ftr || !seeds || !opt || S < 0) return SVO_HIP_EINVAL;
-  if (S == 0) return SVO_HIP_OK;
-  if (!d_slot_of || !d_status || !frames->d_slot || !frames->d_T_f_w || cur_frame < 0 || cur_frame >= frames->n_frames ||
-      !ftr->d_frame || !ftr->d_level || !ftr->d_px || !ftr->d_f || !seeds->d_a || !seeds->d_b || !seeds->d_mu ||
-      !seeds->d_z_range || !seeds->d_sigma2 || !seeds->d_batch_id)
-    return SVO_HIP_EINVAL;
-  if (ftr->d_type && !ftr->d_grad) return SVO_HIP_EINVAL;
-  if (opt->n_pyr_levels < 1 || opt->n_pyr_levels > layout->n_levels || opt->align_max_iter < 0 ||
-      opt->max_epi_search_steps < 0)
-    return SVO_HIP_EINVAL;
+  SeedArgs a{};
+  const int rc = seed_args_begin(a, layout, d_store, cam, frames, S, ftr, seeds, false, opt);
+  if (rc != SVO_HIP_OK) return rc > 0 ? SVO_HIP_OK : rc;
+  if (!d_slot_of || !d_status || cur_frame < 0 || cur_frame >= frames->n_frames) return SVO_HIP_EINVAL;
   if (!d_workspace || workspace_bytes < svo_hip_match_workspace_bytes(S)) return SVO_HIP_ERANGE;
-  SeedArgs a;
-  a.L = *layout;
-  a.store = d_store;
-  a.cam = make_cam(cam);
-  a.S = S;
-  a.frame_slot = frames->d_slot;
-  a.frame_T = frames->d_T_f_w;
-  a.cur_frame = nullptr;
   a.cur_index = cur_frame;
-  a.cur_T_set = T_cur_host != nullptr;
-  for (int k = 0; k < 12; ++k) a.cur_T[k] = T_cur_host ? T_cur_host[k] : 0.0;
+  if (T_cur_host) {
+    a.cur_T_set = 1;
+    for (int k = 0; k < 12; ++k) a.cur_T[k] = T_cur_host[k];
+  }
   a.slot_of = d_slot_of;
   a.state_out = d_state_out;
-  a.ftr = *ftr;
-  a.seeds = *seeds;
-  a.opt = *opt;
   a.status_out = d_status;
   a.xyz_world = d_xyz_world;
   a.px_cur_out = d_px_cur;
-  a.match_only = 0;
-  a.d_est = a.d_min = a.d_max = nullptr;
-  a.depth_out = nullptr;
-  a.ok_out = nullptr;
-  a.search_level_out = nullptr;
   return run_seed_chain(layout, d_store, a, S, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 

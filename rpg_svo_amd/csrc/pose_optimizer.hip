@@ -12,6 +12,10 @@
 // reproduced to the bit wherever the per-observation arithmetic is (no reassociation).
 // Lane 0 runs the 6x6 pivoted LDLT (Eigen's algorithm), the rollback / convergence rules
 // and SE3::exp(dT)*T; medians are found by exact rank counting in LDS (nth_element's value).
+//
+// Entry points: svo_hip_pose_optimize, _deferred and _ordered are one-line calls of pose_optimize_impl with a mode; it checks the
+// arguments, fills one svo_track::PoseWaveArgs and hands it to the wave kernel (pose_optimizer_wave.hip) and / or to
+// launch_ordered, which builds this file's PoseArgs from it.
 #pragma clang fp contract(off)
 #include "track_kernels.h"
 #include "track_math.h"
@@ -377,51 +381,42 @@ __global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_kernel(const PoseA
 
 }  // namespace
 
-static int pose_args_check(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride, const double* d_f,
-                           const int32_t* d_level, const double* d_pos, uint8_t* d_has_point, int n_iter,
-                           double* d_T_f_w, double* d_stats, int32_t* d_ran) {
-  if (!cam || !cam_model_ok(cam) || B < 0 || n_stride < 1 || n_iter < 0) return SVO_HIP_EINVAL;
-  if (n_stride > PO_MAXN) return SVO_HIP_ERANGE;
-  if (B == 0) return 1;
-  if (!d_n || !d_f || !d_level || !d_pos || !d_has_point || !d_T_f_w || !d_stats || !d_ran) return SVO_HIP_EINVAL;
-  return SVO_HIP_OK;
-}
-
-static int launch_ordered(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride, const double* d_f,
-                          const int32_t* d_level, const double* d_pos, uint8_t* d_has_point, double reproj_thresh,
-                          int n_iter, double* d_T_f_w, double* d_Cov, double* d_stats, int32_t* d_ran, int only_flagged,
-                          void* stream) {
+// The ordered kernel on the frames of `w`; only_flagged = 1: on those the wave kernel handed over (ran = 2) alone.
+static int launch_ordered(const svo_track::PoseWaveArgs& w, int only_flagged, hipStream_t s) {
   PoseArgs a;
-  a.cam = make_cam(cam);
-  a.n = d_n;
-  a.n_stride = n_stride;
-  a.f = d_f;
-  a.level = d_level;
-  a.pos = d_pos;
-  a.has_point = d_has_point;
-  a.reproj_thresh = reproj_thresh;
-  a.n_iter = n_iter;
-  a.T = d_T_f_w;
-  a.Cov = d_Cov;
-  a.stats = d_stats;
-  a.ran = d_ran;
+  a.cam = make_cam(&w.cam);
+  a.n = w.n;
+  a.n_stride = w.n_stride;
+  a.f = w.f;
+  a.level = w.level;
+  a.pos = w.pos;
+  a.has_point = w.has_point;
+  a.reproj_thresh = w.reproj_thresh;
+  a.n_iter = w.n_iter;
+  a.T = w.T;
+  a.Cov = w.Cov;
+  a.stats = w.stats;
+  a.ran = w.ran;
   a.only_flagged = only_flagged;
-  const int ns8 = (n_stride + 7) & ~7;
+  const int ns8 = (w.n_stride + 7) & ~7;
   const size_t dyn = (size_t)ns8 * (sizeof(double) + sizeof(float) + 1);
-  hipLaunchKernelGGL(pose_opt_kernel, dim3(B), dim3(PO_BLOCK), dyn, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(pose_opt_kernel, dim3(w.B), dim3(PO_BLOCK), dyn, s, a);
   return check_launch();
 }
 
-// finish: also run the ordered kernel on the frames the wave kernel flags (ran = 2)
-static int pose_optimize_impl(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride, const double* d_f,
+// What an entry does behind the checks.  WAVE_FINISH: the wave kernel, then the ordered kernel on the frames it flags;
+// WAVE_DEFERRED: the wave kernel alone (the caller finishes the flagged frames); ORDERED: the ordered kernel on every frame.
+enum PoseMode { POSE_WAVE_FINISH, POSE_WAVE_DEFERRED, POSE_ORDERED };
+
+// The three entries: one check of the arguments (scalars: EINVAL; n_stride beyond the kernels: ERANGE; the empty batch: OK;
+// the arrays: EINVAL -- in this order), one argument block, one dispatch.
+static int pose_optimize_impl(PoseMode mode, const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride, const double* d_f,
                               const int32_t* d_level, const double* d_pos, uint8_t* d_has_point, double reproj_thresh,
-                              int n_iter, double* d_T_f_w, double* d_Cov, double* d_stats, int32_t* d_ran, bool finish,
-                              void* stream) {
-  const int rc = pose_args_check(cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, n_iter, d_T_f_w, d_stats, d_ran);
-  if (rc != SVO_HIP_OK) return rc > 0 ? SVO_HIP_OK : rc;
-  if (n_stride > svo_track::POSE_WAVE_MAX_STRIDE)  // more than 4 observations per lane: ordered kernel
-    return launch_ordered(cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w, d_Cov,
-                          d_stats, d_ran, 0, stream);
+                              int n_iter, double* d_T_f_w, double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
+  if (!cam || !cam_model_ok(cam) || B < 0 || n_stride < 1 || n_iter < 0) return SVO_HIP_EINVAL;
+  if (n_stride > PO_MAXN) return SVO_HIP_ERANGE;
+  if (B == 0) return SVO_HIP_OK;
+  if (!d_n || !d_f || !d_level || !d_pos || !d_has_point || !d_T_f_w || !d_stats || !d_ran) return SVO_HIP_EINVAL;
   svo_track::PoseWaveArgs w;
   w.cam = *cam;
   w.B = B;
@@ -437,36 +432,36 @@ static int pose_optimize_impl(const svo_hip_camera* cam, int B, const int32_t* d
   w.Cov = d_Cov;
   w.stats = d_stats;
   w.ran = d_ran;
-  const int r2 = svo_track::launch_pose_wave(w, static_cast<hipStream_t>(stream));
-  if (r2 != SVO_HIP_OK || !finish) return r2;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mode == POSE_ORDERED || n_stride > svo_track::POSE_WAVE_MAX_STRIDE)  // (more than 4 observations per lane: ordered kernel)
+    return launch_ordered(w, 0, s);
+  const int rc = svo_track::launch_pose_wave(w, s);
+  if (rc != SVO_HIP_OK || mode == POSE_WAVE_DEFERRED) return rc;
   // frames whose normal equations are (nearly) singular were left untouched and flagged ran = 2:
   // the ordered kernel takes exactly those (its other workgroups exit at once)
-  return launch_ordered(cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w, d_Cov,
-                        d_stats, d_ran, 1, stream);
+  return launch_ordered(w, 1, s);
 }
 
 extern "C" int svo_hip_pose_optimize(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride,
                                      const double* d_f, const int32_t* d_level, const double* d_pos,
                                      uint8_t* d_has_point, double reproj_thresh, int n_iter, double* d_T_f_w,
                                      double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
-  return pose_optimize_impl(cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w, d_Cov,
-                            d_stats, d_ran, true, stream);
+  return pose_optimize_impl(POSE_WAVE_FINISH, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w,
+                            d_Cov, d_stats, d_ran, stream);
 }
 
 extern "C" int svo_hip_pose_optimize_deferred(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride,
                                               const double* d_f, const int32_t* d_level, const double* d_pos,
                                               uint8_t* d_has_point, double reproj_thresh, int n_iter, double* d_T_f_w,
                                               double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
-  return pose_optimize_impl(cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w, d_Cov,
-                            d_stats, d_ran, false, stream);
+  return pose_optimize_impl(POSE_WAVE_DEFERRED, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w,
+                            d_Cov, d_stats, d_ran, stream);
 }
 
 extern "C" int svo_hip_pose_optimize_ordered(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride,
                                              const double* d_f, const int32_t* d_level, const double* d_pos,
                                              uint8_t* d_has_point, double reproj_thresh, int n_iter, double* d_T_f_w,
                                              double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
-  const int rc = pose_args_check(cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, n_iter, d_T_f_w, d_stats, d_ran);
-  if (rc != SVO_HIP_OK) return rc > 0 ? SVO_HIP_OK : rc;
-  return launch_ordered(cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w, d_Cov,
-                        d_stats, d_ran, 0, stream);
+  return pose_optimize_impl(POSE_ORDERED, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w,
+                            d_Cov, d_stats, d_ran, stream);
 }

@@ -315,12 +315,37 @@ static bool tile_ok(int tile_width) {
   return tile_width == 0 || tile_width == 128 || tile_width == 256 || tile_width == 257 || tile_width == 512;
 }
 
+static bool halfsample_ok(int mode) { return mode >= SVO_HIP_HALFSAMPLE_SCALAR && mode <= SVO_HIP_HALFSAMPLE_AUTO; }
+
+// the flavour of the half-sampling that produces level `lvl`: 1 = the SSE2 rounding (AUTO: wherever the source width allows it)
+static int halfsample_sse2(const svo_hip_pyr_layout* L, int lvl, int halfsample_mode) {
+  if (halfsample_mode == SVO_HIP_HALFSAMPLE_AUTO) return (L->w[lvl - 1] % 16) == 0 ? 1 : 0;
+  return halfsample_mode == SVO_HIP_HALFSAMPLE_SSE2 ? 1 : 0;
+}
+
+// levels from_level .. n_levels - 1 of n_slots slots, each from the level above it: one launch per level (and per 32768 slots)
+static int half_sample_levels(const svo_hip_pyr_layout* L, uint8_t* d_store, int first_slot, int n_slots, int from_level,
+                              int halfsample_mode, hipStream_t s) {
+  const dim3 block(64, 4, 1);
+  for (int lvl = from_level; lvl < L->n_levels; ++lvl) {
+    const int sse2 = halfsample_sse2(L, lvl, halfsample_mode);
+    const int out_w = L->w[lvl], out_h = L->h[lvl];
+    int done = 0;
+    while (done < n_slots) {
+      const int chunk = min(n_slots - done, 32768);
+      const dim3 grid(((out_w + 3) / 4 + 63) / 64, (out_h + 3) / 4, chunk);
+      hipLaunchKernelGGL(half_sample_kernel, grid, block, 0, s, d_store, L->slot_bytes, first_slot + done,
+                         L->offset[lvl - 1], L->pitch[lvl - 1], L->offset[lvl], L->pitch[lvl], out_w, out_h, sse2);
+      int rc = check_launch();
+      if (rc) return rc;
+      done += chunk;
+    }
+  }
+  return SVO_HIP_OK;
+}
+
 static int build_impl(const svo_hip_pyr_layout* L, uint8_t* d_store, int first_slot, int n_slots, const uint8_t* d_images,
                       int64_t image_stride, int row_stride, int halfsample_mode, int tile_width, hipStream_t s) {
-  auto flavour = [&](int lvl) {
-    if (halfsample_mode == SVO_HIP_HALFSAMPLE_AUTO) return (L->w[lvl - 1] % 16) == 0 ? 1 : 0;
-    return halfsample_mode == SVO_HIP_HALFSAMPLE_SSE2 ? 1 : 0;
-  };
   FusedArgs a;
   a.store = d_store;
   a.slot_bytes = L->slot_bytes;
@@ -328,7 +353,7 @@ static int build_impl(const svo_hip_pyr_layout* L, uint8_t* d_store, int first_s
   for (int l = 0; l < FUSED_MAX_LEVELS; ++l) {
     const bool on = l < a.n_levels;
     a.w[l] = on ? L->w[l] : 0; a.h[l] = on ? L->h[l] : 0; a.pitch[l] = on ? L->pitch[l] : 0; a.off[l] = on ? L->offset[l] : 0;
-    a.sse2[l] = (on && l > 0) ? flavour(l) : 0;
+    a.sse2[l] = (on && l > 0) ? halfsample_sse2(L, l, halfsample_mode) : 0;
   }
   a.image_stride = image_stride;
   a.row_stride = row_stride;
@@ -357,29 +382,13 @@ static int build_impl(const svo_hip_pyr_layout* L, uint8_t* d_store, int first_s
     done += chunk;
   }
   // levels beyond the fused ones (pyramids deeper than 5 levels): one launch per level
-  const dim3 block(64, 4, 1);
-  for (int lvl = FUSED_MAX_LEVELS; lvl < L->n_levels; ++lvl) {
-    const int sse2 = flavour(lvl);
-    const int out_w = L->w[lvl], out_h = L->h[lvl];
-    done = 0;
-    while (done < n_slots) {
-      const int chunk = min(n_slots - done, 32768);
-      const dim3 grid(((out_w + 3) / 4 + 63) / 64, (out_h + 3) / 4, chunk);
-      hipLaunchKernelGGL(half_sample_kernel, grid, block, 0, s, d_store, L->slot_bytes, first_slot + done,
-                         L->offset[lvl - 1], L->pitch[lvl - 1], L->offset[lvl], L->pitch[lvl], out_w, out_h, sse2);
-      int rc = check_launch();
-      if (rc) return rc;
-      done += chunk;
-    }
-  }
-  return SVO_HIP_OK;
+  return half_sample_levels(L, d_store, first_slot, n_slots, FUSED_MAX_LEVELS, halfsample_mode, s);
 }
 
 int svo_hip_pyramid_build(const svo_hip_pyr_layout* L, uint8_t* d_store, int first_slot, int n_slots,
                           int halfsample_mode, void* stream) {
   if (!layout_ok(L) || !d_store || first_slot < 0 || n_slots < 0) return SVO_HIP_EINVAL;
-  if (halfsample_mode < SVO_HIP_HALFSAMPLE_SCALAR || halfsample_mode > SVO_HIP_HALFSAMPLE_AUTO)
-    return SVO_HIP_EINVAL;
+  if (!halfsample_ok(halfsample_mode)) return SVO_HIP_EINVAL;
   return build_impl(L, d_store, first_slot, n_slots, nullptr, 0, 0, halfsample_mode, 0, static_cast<hipStream_t>(stream));
 }
 
@@ -387,8 +396,7 @@ int svo_hip_pyramid_build_from_images(const svo_hip_pyr_layout* L, uint8_t* d_st
                                       const uint8_t* d_images, int64_t image_stride, int row_stride,
                                       int halfsample_mode, void* stream) {
   if (!layout_ok(L) || !d_store || !d_images || first_slot < 0 || n_slots < 0 || row_stride < L->w[0]) return SVO_HIP_EINVAL;
-  if (halfsample_mode < SVO_HIP_HALFSAMPLE_SCALAR || halfsample_mode > SVO_HIP_HALFSAMPLE_AUTO)
-    return SVO_HIP_EINVAL;
+  if (!halfsample_ok(halfsample_mode)) return SVO_HIP_EINVAL;
   return build_impl(L, d_store, first_slot, n_slots, d_images, image_stride, row_stride, halfsample_mode, 0,
                     static_cast<hipStream_t>(stream));
 }
@@ -398,8 +406,7 @@ int svo_hip_pyramid_build_tiled(const svo_hip_pyr_layout* L, uint8_t* d_store, i
                                 int tile_width, void* stream) {
   if (!layout_ok(L) || !d_store || first_slot < 0 || n_slots < 0 || !tile_ok(tile_width)) return SVO_HIP_EINVAL;
   if (d_images && row_stride < L->w[0]) return SVO_HIP_EINVAL;
-  if (halfsample_mode < SVO_HIP_HALFSAMPLE_SCALAR || halfsample_mode > SVO_HIP_HALFSAMPLE_AUTO)
-    return SVO_HIP_EINVAL;
+  if (!halfsample_ok(halfsample_mode)) return SVO_HIP_EINVAL;
   return build_impl(L, d_store, first_slot, n_slots, d_images, image_stride, row_stride, halfsample_mode, tile_width,
                     static_cast<hipStream_t>(stream));
 }
@@ -408,26 +415,8 @@ int svo_hip_pyramid_build_tiled(const svo_hip_pyr_layout* L, uint8_t* d_store, i
 int svo_hip_pyramid_build_per_level(const svo_hip_pyr_layout* L, uint8_t* d_store, int first_slot, int n_slots,
                                     int halfsample_mode, void* stream) {
   if (!layout_ok(L) || !d_store || first_slot < 0 || n_slots < 0) return SVO_HIP_EINVAL;
-  if (halfsample_mode < SVO_HIP_HALFSAMPLE_SCALAR || halfsample_mode > SVO_HIP_HALFSAMPLE_AUTO)
-    return SVO_HIP_EINVAL;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 block(64, 4, 1);
-  for (int lvl = 1; lvl < L->n_levels; ++lvl) {
-    int sse2 = halfsample_mode == SVO_HIP_HALFSAMPLE_SSE2;
-    if (halfsample_mode == SVO_HIP_HALFSAMPLE_AUTO) sse2 = (L->w[lvl - 1] % 16) == 0;
-    const int out_w = L->w[lvl], out_h = L->h[lvl];
-    int done = 0;
-    while (done < n_slots) {
-      const int chunk = min(n_slots - done, 32768);
-      const dim3 grid(((out_w + 3) / 4 + 63) / 64, (out_h + 3) / 4, chunk);
-      hipLaunchKernelGGL(half_sample_kernel, grid, block, 0, s, d_store, L->slot_bytes, first_slot + done,
-                         L->offset[lvl - 1], L->pitch[lvl - 1], L->offset[lvl], L->pitch[lvl], out_w, out_h, sse2);
-      int rc = check_launch();
-      if (rc) return rc;
-      done += chunk;
-    }
-  }
-  return SVO_HIP_OK;
+  if (!halfsample_ok(halfsample_mode)) return SVO_HIP_EINVAL;
+  return half_sample_levels(L, d_store, first_slot, n_slots, 1, halfsample_mode, static_cast<hipStream_t>(stream));
 }
 
 // A new camera frame in one go: H2D copy of the image into packed scratch, then ONE kernel that writes level 0
@@ -435,8 +424,7 @@ int svo_hip_pyramid_build_per_level(const svo_hip_pyr_layout* L, uint8_t* d_stor
 int svo_hip_pyramid_upload_build(const svo_hip_pyr_layout* L, uint8_t* d_store, int slot, const uint8_t* image,
                                  int row_stride, int halfsample_mode, void* d_staging, void* stream) {
   if (!layout_ok(L) || !d_store || !image || slot < 0 || row_stride < L->w[0]) return SVO_HIP_EINVAL;
-  if (halfsample_mode < SVO_HIP_HALFSAMPLE_SCALAR || halfsample_mode > SVO_HIP_HALFSAMPLE_AUTO)
-    return SVO_HIP_EINVAL;
+  if (!halfsample_ok(halfsample_mode)) return SVO_HIP_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int w = L->w[0], h = L->h[0];
   Staging st(s);

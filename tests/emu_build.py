@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE.  The host-emulated build of the C-ABI library: the .hip translation units of rpg_svo_amd/csrc compiled by
 ROCm's clang++ as plain C++ through tests/host/hip_emu.h (work-items as fibers, barriers, LDS, cross-lane rendezvous) and
-linked into build/libsvo_hip_emulated[_<defines>].so.  The same entry points as libsvo_hip.so, on host memory; no timing."""
+linked into build/emu/libsvo_hip_emulated[_<defines>][_<sanitizer>].so: ONE library with every kernel family, the entry points of
+libsvo_hip.so's kernel files on host memory; no timing."""
 import ctypes as C
 import glob
 import os
@@ -10,7 +11,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNITS = ("common", "pyramid", "map_mirror", "matcher", "feature_align", "depth_filter", "sparse_align", "sparse_align_wave",
-         "pose_optimizer_wave", "pose_optimizer", "point_optimizer", "fast_detect")
+         "pose_optimizer_wave", "pose_optimizer", "point_optimizer", "fast_detect", "klt_track", "homography_init")
 
 
 # Compile-time variants of the library the emulated parity tests run on besides the default build (round 4 queued ten of
@@ -34,25 +35,39 @@ def llvm_bin():
     return os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin")
 
 
+def _cxx():
+    return os.path.join(llvm_bin(), "clang++")
+
+
+def _sanitizer_flags(san):
+    """compile and link flags of a build instrumented by sanitizer `san` ("": none)"""
+    if not san:
+        return []
+    flags = [f"-fsanitize={san}", "-shared-libsan", "-fno-omit-frame-pointer", "-g"]
+    if san == "undefined":
+        # + float-cast-overflow (a float -> int conversion out of range: the kernels guard theirs to reproduce cvttss2si).
+        # float-divide-by-zero stays off: IEEE defines it and the kernels rely on it where the reference does (1 / tau2 with
+        # tau2 = 0, the inverse of a singular H, chi2 / n_meas with nothing tracked: six sites, all the reference's own)
+        flags += ["-fsanitize=float-cast-overflow", "-fno-sanitize=vptr,function"]
+    return flags
+
+
 def sanitizer_runtime(kind):
-    cxx = os.path.join(llvm_bin(), "clang++")
     name = {"address": "asan", "thread": "tsan", "undefined": "ubsan_standalone"}[kind]
-    out = subprocess.run([cxx, f"-print-file-name=libclang_rt.{name}-x86_64.so"], capture_output=True, text=True).stdout.strip()
+    out = subprocess.run([_cxx(), f"-print-file-name=libclang_rt.{name}-x86_64.so"], capture_output=True, text=True).stdout.strip()
     return out if os.path.isabs(out) and os.path.exists(out) else None
 
 
 def build_race_probe():
     """tests/host/emu_race_probe.cpp (a kernel with and without the barrier it needs) with the sanitizer of SVO_EMU_SANITIZE."""
     san = sanitizer()
-    cxx = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
     lib_path = os.path.join(ROOT, "build", "emu", f"libemu_race_probe_{san or 'plain'}.so")
     src = os.path.join(ROOT, "tests", "host", "emu_race_probe.cpp")
     hdr = os.path.join(ROOT, "tests", "host", "hip_emu.h")
     os.makedirs(os.path.dirname(lib_path), exist_ok=True)
     if not os.path.exists(lib_path) or os.path.getmtime(lib_path) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        flags = [f"-fsanitize={san}", "-shared-libsan", "-fno-omit-frame-pointer", "-g"] if san else []
-        subprocess.run([cxx, "-std=c++17", "-O1", "-fPIC", "-shared", *flags, "-I", os.path.join(ROOT, "tests", "host"), src, "-o", lib_path],
-                       check=True)
+        subprocess.run([_cxx(), "-std=c++17", "-O1", "-fPIC", "-shared", *_sanitizer_flags(san), "-I", os.path.join(ROOT, "tests", "host"),
+                        src, "-o", lib_path], check=True)
     lib = C.CDLL(lib_path)
     lib.probe_neighbour_sum.restype = C.c_int
     lib.probe_neighbour_sum.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
@@ -68,19 +83,14 @@ def build_emulated(defines=()):
         import hashlib
         tag = "_set" + hashlib.sha1(tag.encode()).hexdigest()[:10]
     san = sanitizer()
-    san_flags = [f"-fsanitize={san}", "-shared-libsan", "-fno-omit-frame-pointer", "-g"] if san else []
-    if san == "undefined":
-        # + float-cast-overflow (a float -> int conversion out of range: the kernels guard theirs to reproduce cvttss2si).
-        # float-divide-by-zero stays off: IEEE defines it and the kernels rely on it where the reference does (1 / tau2 with
-        # tau2 = 0, the inverse of a singular H, chi2 / n_meas with nothing tracked: six sites, all the reference's own)
-        san_flags += ["-fsanitize=float-cast-overflow", "-fno-sanitize=vptr,function"]
+    san_flags = _sanitizer_flags(san)
     if san:
         tag += "_" + san
     lib_path = os.path.join(ROOT, "build", "emu", f"libsvo_hip_emulated{tag}.so")
     objdir = os.path.join(ROOT, "build", "emu", f"obj{tag}")
     os.makedirs(objdir, exist_ok=True)
     csrc = os.path.join(ROOT, "rpg_svo_amd", "csrc")
-    cxx = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
+    cxx = _cxx()
     if not os.path.exists(cxx):
         pytest.skip("no ROCm clang++ to compile the kernels for the host")
     deps = glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + \

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: rpg_svo_amd/csrc/klt_track.hip compiled for the host (tests/host/hip_emu.h); tests/klt_emu_build.py links it
-// with the common, pyramid and matcher units of the emulated build.
+// TEST INFRASTRUCTURE: rpg_svo_amd/csrc/klt_track.hip compiled for the host (tests/host/hip_emu.h); part of the emulated build of
+// the C-ABI library that tests/emu_build.py links.
 #include "hip_emu.h"
 #include "../../rpg_svo_amd/csrc/klt_track.hip"

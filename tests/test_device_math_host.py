@@ -18,6 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import pyoracle  # noqa: E402
+import emu_build  # noqa: E402
 
 SRC = os.path.join(ROOT, "tests", "host", "device_math_on_host.cpp")
 LIB = os.path.join(ROOT, "build", "emu", "libdevice_math_on_host.so")
@@ -35,7 +36,7 @@ def _build_host_lib(lib_path, defines=()):
                     for h in ("device_math.h", "track_math.h", "matcher_device.h", "seed_math.h", "align_lanes.h", "pyr_addr.h", "warp_sample.h")]
     if not os.path.exists(lib_path) or any(os.path.getmtime(d) > os.path.getmtime(lib_path) for d in deps):
         # ROCm's clang++ as a plain C++ compiler for the host (the lane bodies use clang's ext_vector_type pairs)
-        cxx = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
+        cxx = os.path.join(emu_build.llvm_bin(), "clang++")
         if not os.path.exists(cxx):
             pytest.skip("no ROCm clang++ to compile the kernels' headers for the host")
         subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-fno-math-errno", "-fPIC", "-shared", "-Wall",

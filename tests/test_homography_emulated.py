@@ -1,4 +1,4 @@
-"""svo_hip_homography_init of the host-emulated build (tests/homography_emu_build.py: homography_init.hip compiled for the
+"""svo_hip_homography_init of the host-emulated build (tests/emu_build.py: homography_init.hip compiled for the
 CPU through tests/host/hip_emu.h, one fiber per work-item, the wave exchanges as rendezvous) on the cases of
 tests/homography_cases.py against the f64 checker (tests/homography_checker.py), by the rule homography_cases.py states.
 
@@ -21,8 +21,8 @@ BOUND = 100 * MEASURED_EMULATION      # 2.95e-9 relative; the device test uses t
 
 @pytest.fixture(scope="module")
 def emu():
-    from homography_emu_build import build_emulated_homography
-    return build_emulated_homography()
+    from emu_build import build_emulated
+    return build_emulated(())
 
 
 def _p(a):

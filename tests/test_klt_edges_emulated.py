@@ -1,4 +1,4 @@
-"""svo_hip_klt_track and svo_hip_klt_summarize of the host-emulated build (tests/klt_emu_build.py) on the inputs of
+"""svo_hip_klt_track and svo_hip_klt_summarize of the host-emulated build (tests/emu_build.py) on the inputs of
 tests/klt_edge_cases.py: windows over every border and corner of small and odd-sized levels, both loaders of
 klt_track.hip and the switch between them, the bounds rule at its exact limits, hostile initial flow, every parameter away
 from its default, coarse levels skipped by the min-eigenvalue rule, batch indexing, and the summary step at the sizes
@@ -23,8 +23,8 @@ from test_klt_emulated import _p, build_store, default_params, klt_track
 
 @pytest.fixture(scope="module")
 def emu():
-    from klt_emu_build import build_emulated_klt
-    return build_emulated_klt()
+    from emu_build import build_emulated
+    return build_emulated(())
 
 
 def run(emu, c):

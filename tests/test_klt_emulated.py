@@ -1,5 +1,5 @@
 """The bootstrap's tracker without a GPU: svo_hip_klt_track and svo_hip_klt_summarize of the host-emulated build
-(tests/klt_emu_build.py: klt_track.hip compiled for the CPU through tests/host/hip_emu.h, one fiber per lane, the wave's
+(tests/emu_build.py: klt_track.hip compiled for the CPU through tests/host/hip_emu.h, one fiber per lane, the wave's
 exchanges as rendezvous) against the f64 checker (tests/klt_checker.py) on a 376 x 240 camera, 5 levels, 48 corners, frame 0
 tracked into the following frames with the carried flow.
 
@@ -24,8 +24,8 @@ from rpg_svo_amd import capi
 
 @pytest.fixture(scope="module")
 def emu():
-    from klt_emu_build import build_emulated_klt
-    return build_emulated_klt()
+    from emu_build import build_emulated
+    return build_emulated(())
 
 
 def _p(a):

@@ -9,6 +9,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+import emu_build
 from helpers import FUZZ, fuzz_rng
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +32,7 @@ def emu():
                                                                        ("epi_scan.h", "track_math.h", "device_math.h", "pyr_addr.h", "matcher_device.h",
                                                                         "warp_group.h", "warp_sample.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        cxx = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
+        cxx = os.path.join(emu_build.llvm_bin(), "clang++")
         if not os.path.exists(cxx):
             pytest.skip("no ROCm clang++ to compile the kernels' headers for the host")
         subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-fno-math-errno", "-fPIC", "-shared", "-pthread", "-Wall",
