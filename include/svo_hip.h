@@ -202,6 +202,9 @@ typedef struct svo_hip_sia_params {
  * with n_stride <= 192 (<= 64 under a distorted camera model) run one WAVE per
  * problem, a lane carrying up to three patches (sparse_align_wave.hip).  Same arithmetic per patch; the order of the
  * (tolerance-mode, f32) sums differs between the two.
+ * The reference-width build of the library (-DSIA_F64_PARTIALS: per-pixel products, patch sums and SE3::exp in f64) covers
+ * the workgroup-per-problem kernel in every size and the frame split over four workgroups; the wave-per-problem path does not
+ * read the define and is the same code, f32 products included, in both libraries.
  *
  *   d_ref_slot/d_cur_slot [B]   pyramid-store slots of the two frames
  *   d_n [B]                     features of problem b (<= n_stride <= SVO_HIP_MAX_PATCHES)

@@ -20,8 +20,11 @@ UNITS = ("common", "pyramid", "map_mirror", "matcher", "feature_align", "depth_f
 # Round 6: ("ALIGN_WAVE_MAX_M_VALUE=0",) -- no batch is small enough for the wave-per-trial alignment, so the depth filter's
 # small test batches take the lane-per-trial kernel WITH the seed_finish epilogue (csrc/seed_finish.h), the path of replay
 # batches beyond 8192 seeds.
-BUILDS = [(), ("ALIGN_WAVE_MAX_M_VALUE=0",)]
-BUILD_IDS = ["default", "lane_kernel_with_finish"]
+# ("SIA_F64_PARTIALS",) -- the reference-width build of K1 (csrc/sparse_align.hip: per-pixel products, patch sums and SE3::exp
+# in f64, the scalar pixel loop instead of the packed one), the library behind the benchmark's `roofline_f64_build` figure.
+# Only sparse_align.hip reads the define: the K1 tests (test_sparse_align_emulated.py, test_emulated_shapes.py) run builds 0 and 2.
+BUILDS = [(), ("ALIGN_WAVE_MAX_M_VALUE=0",), ("SIA_F64_PARTIALS",)]
+BUILD_IDS = ["default", "lane_kernel_with_finish", "reference_width"]
 
 
 def sanitizer():

@@ -1,12 +1,13 @@
 """Odd shapes through the emulated kernels (tests/emu_build.py): image sizes that are no multiple of the store's 16 x 8 tiles,
 of a workgroup's footprint or of anything else, levels down to a few pixels, grid cells larger than the image, frames with
-9 ... 300 patches (every workgroup size of K1) -- each against the oracle, bit for bit where the GPU tests ask for that.  The
+9 ... 520 patches (every workgroup size of K1, at both of its widths) -- each against the oracle, bit for bit where the GPU tests ask for that.  The
 border arithmetic is where an out-of-bounds access would hide: scripts/emu_sanitize.sh runs this file under
 AddressSanitizer, too."""
 import numpy as np
 import pytest
 
-from helpers import make_batch, run_oracle
+import k1_width_cases
+from helpers import run_oracle
 from oracle import pytrack
 from rpg_svo_amd import capi, se3, synth
 from test_fast_emulated import detect
@@ -60,18 +61,33 @@ def test_fast_on_any_shape(emu, oracle, w, h, levels, cell):
         assert np.array_equal(xy[i], exy) and np.array_equal(lvl[i], elvl)
 
 
-@pytest.mark.parametrize("w,h,n,levels,lo,hi", [(160, 120, 9, 3, 0, 2), (200, 150, 65, 3, 1, 2), (322, 242, 129, 4, 0, 3),
-                                                (328, 248, 257, 4, 2, 3), (336, 256, 300, 3, 0, 2)])
-def test_sparse_align_on_any_shape(emu, oracle, w, h, n, levels, lo, hi):
-    """(64-, 128-, 256- and 512-lane workgroups; a frame with a third of the patches in the middle of the batch)"""
-    cam = synth.Camera(w, h, w * 0.6, w * 0.6, w / 2.0, h / 2.0)
-    seq = synth.make_sequence(4, n, cam=cam, seed=n, margin=12, cell=max(8, int((w * h / n) ** 0.5 * 0.7)))
-    b = make_batch(seq, [(0, 1), (1, 2), (2, 3)], levels)
-    b.n[1] = max(6, n // 3)
+@pytest.fixture(scope="module")
+def emu_reference_width():
+    """the reference-width build of K1 (emu_build.BUILDS[2]: -DSIA_F64_PARTIALS)"""
+    from emu_build import BUILDS, build_emulated
+    return build_emulated(BUILDS[2])
+
+
+def _sparse_align_on_a_shape(emu, oracle, shape):
+    b, (hi, lo, n_iter) = k1_width_cases.shape_case(*shape)
     T_o, res_o, _ = run_oracle(oracle, b, hi, lo)
     T_h, ntr, iters, H, status = run_emulated(emu, b, hi, lo)
     assert se3.log_norm(T_h, T_o).max() <= 1e-4
     assert np.array_equal(ntr, np.array([r["n_tracked"] for r in res_o]))
+
+
+@pytest.mark.parametrize("w,h,n,levels,lo,hi", k1_width_cases.SHAPES)
+def test_sparse_align_on_any_shape(emu, oracle, w, h, n, levels, lo, hi):
+    """(64-, 128-, 256-, 512- and 1024-lane workgroups; a frame with a third of the patches in the middle of the batch -- 513 of
+    520 for the 1024-lane one, so that it stays above 512)"""
+    _sparse_align_on_a_shape(emu, oracle, (w, h, n, levels, lo, hi))
+
+
+@pytest.mark.parametrize("w,h,n,levels,lo,hi", k1_width_cases.SHAPES)
+def test_sparse_align_on_any_shape_at_reference_width(emu_reference_width, oracle, w, h, n, levels, lo, hi):
+    """the same shapes and asserts on the -DSIA_F64_PARTIALS build: f64 products and SE3::exp, the scalar pixel loop, in every
+    workgroup size"""
+    _sparse_align_on_a_shape(emu_reference_width, oracle, (w, h, n, levels, lo, hi))
 
 
 @pytest.mark.parametrize("kind", ["pinhole", "atan"])
