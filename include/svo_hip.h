@@ -930,6 +930,101 @@ int svo_hip_homography_init(const svo_hip_camera* cam, int n_pairs, int n_pts, c
                             const svo_hip_homography_params* params, const svo_hip_homography_out* out,
                             void* stream);
 
+/* ---- K10: two-view bootstrap, first map and seeds (frame_handler_mono.cpp:103-127) ------------------------- */
+/*
+ * What FrameHandlerMono::processSecondFrame does with a SUCCESS of addSecondFrame before the first processFrame, for
+ * n_seq sequences of n_pts corners each, in two entries with svo_hip_fast_detect between them.  All of it is f64 with
+ * separate roundings; sequential scans of the reference are stated as arg-max / arg-min rules, so the outputs are the
+ * bits of tests/first_map_checker.py's sequential loops.
+ *
+ * svo_hip_first_map.  Inputs per sequence (what K8 / K9 and the gates leave): d_result [n_seq] i32, the final
+ * InitResult (K9's d_result where both gates passed, the gate's result elsewhere); d_point_ok [n_pts] u8, d_point_w
+ * [n_pts][3], d_px_ref / d_px_cur [n_pts][2] f32, d_f_ref / d_f_cur [n_pts][3], d_T_ref_w / d_T_cur_w [12] (d_T_ref_w
+ * belongs to the state but is not read: nothing below depends on the reference frame's pose).  cam gives width and
+ * height only.  A sequence whose result is not SVO_HIP_INIT_SUCCESS has n_points = 0.
+ *  1. Map (initialization.cpp:78-97).  The corners with point_ok != 0, in index order, have ranks 0 .. n_points - 1:
+ *     the reference's inliers_ order.  src_index[rank] = corner index.  pos[rank] = point_w (Point::pos_); view 0 is
+ *     the reference frame's Feature, view 1 the current frame's: px = the f32 pixel widened to f64, f = the stored
+ *     bearing, level 0.
+ *  2. Key points (setKeyframe() of both frames: Frame::checkKeyPoints over the features in rank order, on frames that
+ *     had none).  cu = width / 2, cv = height / 2 (integer division), dx = px0 - cu, dy = px1 - cv.  Per view:
+ *       key_pts[0] = arg-min over all ranks of max(|dx|, |dy|)   (std::max: the second operand when it is larger)
+ *       key_pts[1] = arg-max of dx dy over the ranks with px0 >= cu and px1 >= cv
+ *       key_pts[2] = arg-max of dx dy over the ranks with px0 >= cu and px1 <  cv
+ *       key_pts[3] = arg-max of dx dy over the ranks with px0 <  cv and px1 <  cv   (cv, as frame.cpp:110 has it)
+ *       key_pts[4] = arg-max of dx dy over the ranks with px0 <  cv and px1 >= cv   (cv, as frame.cpp:118 has it)
+ *     Ties go to the smallest rank (the reference replaces on a strict comparison only); -0 and +0 tie.  An empty set
+ *     gives -1 (NULL).  On a non-square image a feature may belong to no quadrant or to two.  A NaN value never wins a
+ *     strict comparison: when the first member's value is NaN it stays the key point, otherwise NaN members are passed
+ *     over.
+ *  3. Scene depth (frame_utils::getSceneDepth of the current frame): z[rank] = (T_cur_w * pos).z with T_cur_w as a unit
+ *     quaternion and a translation (csrc/track_math.h: se3_from_Rt, se3_apply).  depth_min = fmin over the ranks,
+ *     starting from DBL_MAX; depth_mean = the element of rank floor(n_points / 2) in ascending order (vk::getMedian;
+ *     ties by rank).  n_points == 0: both are 0 (the reference warns and leaves them unset).
+ *  4. xyz_ref[rank] = f_cur * sqrt((dx dx + dy dy) + dz dz), d = pos - T_cur_w.inverse().translation(): what
+ *     SparseImgAlign needs of the current frame as the next reference (sparse_img_align.cpp:107-108).
+ *  5. occupancy (AbstractDetector::setExistingFeatures of the current frame's features): cell
+ *     int(px1 / cell_size) * grid_n_cols + int(px0 / cell_size) is set to 1, every other cell is 0.  A pixel that is
+ *     not finite, or whose row / column index lies outside [0, grid_n_rows) / [0, grid_n_cols), sets no cell (the
+ *     reference's .at() would throw, or wrap a column beyond the grid into the next row).
+ * Beyond n_points: src_index is -1, pos / px / f / xyz_ref are 0.  Every element of every output is written by the
+ * launch.  One workgroup per sequence, integer atomics only: the same call gives the same bits, and so do identical
+ * sequences at different batch positions.
+ * Limits: a null pointer, a negative size, cell_size <= 0 or cells != grid_n_cols * grid_n_rows: SVO_HIP_EINVAL;
+ * n_pts > 1024: SVO_HIP_ERANGE; n_seq * n_pts == 0 is a successful no-op that touches nothing.
+ */
+typedef struct svo_hip_first_map_out {
+  int32_t* d_n_points;  /* [n_seq]                                         */
+  int32_t* d_src_index; /* [n_seq][n_pts]                                  */
+  double* d_pos;        /* [n_seq][n_pts][3]                               */
+  double* d_px;         /* [n_seq][2][n_pts][2]                            */
+  double* d_f;          /* [n_seq][2][n_pts][3]                            */
+  int32_t* d_key_pts;   /* [n_seq][2][5] ranks, -1 = NULL                  */
+  double* d_depth_mean; /* [n_seq]                                         */
+  double* d_depth_min;  /* [n_seq]                                         */
+  double* d_xyz_ref;    /* [n_seq][n_pts][3]                               */
+  uint8_t* d_occupancy; /* [n_seq][cells], svo_hip_fast_detect's d_occupancy */
+} svo_hip_first_map_out;
+int svo_hip_first_map(const svo_hip_camera* cam, int n_seq, int n_pts, const int32_t* d_result,
+                      const uint8_t* d_point_ok, const double* d_point_w, const float* d_px_ref,
+                      const float* d_px_cur, const double* d_f_ref, const double* d_f_cur, const double* d_T_ref_w,
+                      const double* d_T_cur_w, int cell_size, int grid_n_cols, int grid_n_rows, int cells,
+                      const svo_hip_first_map_out* out, void* stream);
+/*
+ * svo_hip_initialize_seeds.  DepthFilter::initializeSeeds after detect (depth_filter.cpp:114-132) for n_frames
+ * keyframes: d_corner_xy / d_corner_level / d_corner_score [n_frames][n_cells] and detection_threshold are
+ * svo_hip_fast_detect's; the cells with (double)score > detection_threshold become, in cell order, records
+ * 0 .. n_seeds - 1 of the frame's seed_stride (>= n_cells) records:
+ *   Feature(frame, px, level) (feature.h:42-50): frame = d_frame_index[frame], px = (x, y) as f64, level, f =
+ *     cam2world(px) with svo_hip_cam2world's bits, type CORNER and grad (1, 0) where d_type / d_grad are given;
+ *   Seed(ftr, float depth_mean, float depth_min) (depth_filter.cpp:37-46) with d_depth_mean / d_depth_min [n_frames]
+ *     f64 as addKeyframe receives them (the caller has halved the minimum), rounded to f32 first: a = b = 10,
+ *     mu = float(1.0 / depth_mean), z_range = float(1.0 / depth_min) (f64 divisions), sigma2 = z_range * z_range / 36
+ *     in f32, batch_id = the value of Seed::batch_counter after its increment.
+ * The records n_seeds .. seed_stride - 1 are zeroed, so every element is written.  Any n_cells: 256 cells at a time
+ * with a running offset.  A null pointer (d_type and d_grad excepted), a negative size, seed_stride < n_cells or an
+ * unknown camera model: SVO_HIP_EINVAL; n_frames == 0 is a successful no-op.
+ */
+typedef struct svo_hip_seed_init_out {
+  int32_t* d_n_seeds;  /* [n_frames]                                                            */
+  int32_t* d_frame;    /* [n_frames][seed_stride]: these six are svo_hip_features' columns      */
+  int32_t* d_level;
+  uint8_t* d_type;     /* may be NULL                                                           */
+  double* d_px;        /* [..][2]                                                               */
+  double* d_f;         /* [..][3]                                                               */
+  double* d_grad;      /* [..][2], may be NULL                                                  */
+  float* d_a;          /* [n_frames][seed_stride]: these six are svo_hip_seeds' columns         */
+  float* d_b;
+  float* d_mu;
+  float* d_z_range;
+  float* d_sigma2;
+  int32_t* d_batch_id;
+} svo_hip_seed_init_out;
+int svo_hip_initialize_seeds(const svo_hip_camera* cam, int n_frames, int n_cells, const int32_t* d_corner_xy,
+                             const int32_t* d_corner_level, const float* d_corner_score, double detection_threshold,
+                             const int32_t* d_frame_index, const double* d_depth_mean, const double* d_depth_min,
+                             int batch_id, int seed_stride, const svo_hip_seed_init_out* out, void* stream);
+
 /* static DepthFilter::computeTau(T_ref_cur, f, z, px_error_angle) (depth_filter.cpp:334-350) for S
  * independent measurements: d_t_ref_cur [S][3] = T_ref_cur.translation(), d_f [S][3], d_z [S].
  * Arithmetic (since round 5, here and inside svo_hip_update_seeds*): the ALGEBRAIC form -- alpha and beta enter only

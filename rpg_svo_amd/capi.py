@@ -127,7 +127,25 @@ class HomographyOut(C.Structure):
     _fields_ = [("d_" + n, C.c_void_p) for n in HOMOGRAPHY_OUTPUTS]
 
 
+FIRST_MAP_OUTPUTS = ("n_points", "src_index", "pos", "px", "f", "key_pts", "depth_mean", "depth_min", "xyz_ref", "occupancy")
+
+
+class FirstMapOut(C.Structure):
+    """svo_hip_first_map_out: outputs of svo_hip_first_map (device pointers)."""
+    _fields_ = [("d_" + n, C.c_void_p) for n in FIRST_MAP_OUTPUTS]
+
+
+SEED_INIT_OUTPUTS = ("n_seeds", "frame", "level", "type", "px", "f", "grad", "a", "b", "mu", "z_range", "sigma2", "batch_id")
+
+
+class SeedInitOut(C.Structure):
+    """svo_hip_seed_init_out: outputs of svo_hip_initialize_seeds (device pointers): n_seeds, then the columns of
+    svo_hip_features and svo_hip_seeds."""
+    _fields_ = [("d_" + n, C.c_void_p) for n in SEED_INIT_OUTPUTS]
+
+
 INIT_FAILURE, INIT_NO_KEYFRAME, INIT_SUCCESS = 0, 1, 2
+FIRST_MAP_MAX_PTS = 1024
 HOMOGRAPHY_OK, HOMOGRAPHY_NO_MODEL, HOMOGRAPHY_DEGENERATE = 0, 1, 2
 HOMOGRAPHY_MAX_PTS, HOMOGRAPHY_MAX_HYPOTHESES = 1024, 4096
 
@@ -233,6 +251,10 @@ PROTOTYPES = {
     "svo_hip_homography_params_default": (_i, [C.POINTER(HomographyParams)]),
     "svo_hip_homography_init": (_i, [C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(HomographyParams),
                                      C.POINTER(HomographyOut), _vp]),
+    "svo_hip_first_map": (_i, [C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                               C.POINTER(FirstMapOut), _vp]),
+    "svo_hip_initialize_seeds": (_i, [C.POINTER(Camera), _i, _i, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _i, _i,
+                                      C.POINTER(SeedInitOut), _vp]),
     "svo_hip_compute_tau_batch": (_i, [_i, _vp, _vp, _vp, C.c_double, _vp, _vp]),
 }
 

@@ -11,13 +11,14 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+from dataclasses import dataclass
 
 import torch
 
 from . import capi
 from .feature_detection import FastDetector
 from .pyramid import PyramidStore, _stream_ptr
-from .tracking import cam2world
+from .tracking import DepthFilter, FeatureSet, SeedSet, cam2world
 
 
 class InitResult(enum.IntEnum):
@@ -110,6 +111,63 @@ def homography_init(cam, f_ref, f_cur, status, px_ref, px_cur, T_ref_w, params=N
     return out
 
 
+@dataclass
+class FirstMap:
+    """The tracking-ready state after the bootstrap (svo_hip_first_map, then the detector and svo_hip_initialize_seeds),
+    for n sequences of m corners.  Ranks are the reference's inliers_ order; view 0 is the reference frame, view 1 the
+    current frame (the next reference of SparseImgAlign: px[:, 1], xyz_ref and n_points are K1's inputs as they are)."""
+    n_points: torch.Tensor     # [n] i32
+    src_index: torch.Tensor    # [n, m] i32 rank -> corner index, -1 beyond n_points
+    pos: torch.Tensor          # [n, m, 3] f64 Point::pos_
+    px: torch.Tensor           # [n, 2, m, 2] f64 Feature::px per view
+    f: torch.Tensor            # [n, 2, m, 3] f64 Feature::f per view
+    key_pts: torch.Tensor      # [n, 2, 5] i32 ranks of Frame::key_pts_, -1 = NULL
+    depth_mean: torch.Tensor   # [n] f64 getSceneDepth of the current frame
+    depth_min: torch.Tensor    # [n] f64
+    xyz_ref: torch.Tensor      # [n, m, 3] f64
+    occupancy: torch.Tensor    # [n, cells] u8 setExistingFeatures of the current frame
+    seed_ftr: FeatureSet | None = None   # [n, cells(, .)] the new corners of the second keyframe, n_seeds per sequence
+    seeds: SeedSet | None = None         # [n, cells] their svo::Seed state
+    n_seeds: torch.Tensor | None = None  # [n] i32
+
+
+_FIRST_MAP_DTYPES = dict(n_points=torch.int32, src_index=torch.int32, pos=torch.float64, px=torch.float64, f=torch.float64,
+                         key_pts=torch.int32, depth_mean=torch.float64, depth_min=torch.float64, xyz_ref=torch.float64,
+                         occupancy=torch.uint8)
+
+
+def first_map_outputs(n: int, m: int, cells: int, device) -> FirstMap:
+    """The tensors of svo_hip_first_map_out.  Allocate once and hand them to every call that a HIP graph captures."""
+    shape = dict(src_index=(n, m), pos=(n, m, 3), px=(n, 2, m, 2), f=(n, 2, m, 3), key_pts=(n, 2, 5), xyz_ref=(n, m, 3),
+                 occupancy=(n, cells))
+    return FirstMap(**{k: torch.zeros(shape.get(k, (n,)), dtype=dt, device=device) for k, dt in _FIRST_MAP_DTYPES.items()})
+
+
+def first_map(cam, result, point_ok, point_w, px_ref, px_cur, f_ref, f_cur, T_ref_w, T_cur_w, cell_size: int, grid_n_cols: int,
+              grid_n_rows: int, out: FirstMap | None = None) -> FirstMap:
+    """svo_hip_first_map on tensors: result [n] i32, point_ok [n, m] u8, point_w / f_ref / f_cur [n, m, 3] f64, px_ref /
+    px_cur [n, m, 2] f32, T_ref_w / T_cur_w [n, 12] f64.  Enqueued on the current stream, not synchronised."""
+    n, m = point_ok.shape
+    for t, dt, shape in ((result, torch.int32, (n,)), (point_ok, torch.uint8, (n, m)), (point_w, torch.float64, (n, m, 3)),
+                         (px_ref, torch.float32, (n, m, 2)), (px_cur, torch.float32, (n, m, 2)), (f_ref, torch.float64, (n, m, 3)),
+                         (f_cur, torch.float64, (n, m, 3)), (T_ref_w, torch.float64, (n, 12)), (T_cur_w, torch.float64, (n, 12))):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape
+    dev = point_ok.device
+    cells = grid_n_cols * grid_n_rows
+    out = first_map_outputs(n, m, cells, dev) if out is None else out
+    for k, dt in _FIRST_MAP_DTYPES.items():
+        t = getattr(out, k)
+        assert t.dtype == dt and t.is_contiguous() and t.device == dev
+    assert tuple(out.occupancy.shape) == (n, cells) and tuple(out.src_index.shape) == (n, m)
+    o = capi.FirstMapOut(*[getattr(out, k).data_ptr() for k in capi.FIRST_MAP_OUTPUTS])
+    c = capi.camera(cam)
+    capi.check(capi.load().svo_hip_first_map(C.byref(c), n, m, result.data_ptr(), point_ok.data_ptr(), point_w.data_ptr(),
+                                             px_ref.data_ptr(), px_cur.data_ptr(), f_ref.data_ptr(), f_cur.data_ptr(),
+                                             T_ref_w.data_ptr(), T_cur_w.data_ptr(), cell_size, grid_n_cols, grid_n_rows, cells,
+                                             C.byref(o), _stream_ptr(dev)), "svo_hip_first_map")
+    return out
+
+
 class KltTracker:
     """KltHomographyInit up to computeHomography, for n sequences at once.  The defaults are the reference's Config
     values (gridSize 30, nPyrLevels 3, initMinTracked 50, initMinDisparity 50, triangMinCornerScore 20)."""
@@ -173,6 +231,7 @@ class KltHomographyInit(KltTracker):
         self.homography_params = homography_params(**(homography or {}))
         self.T_ref_w = None
         self.out = None
+        self.result = None
 
     def add_first_frame(self, store: PyramidStore, slots: torch.Tensor, T_ref_w: torch.Tensor | None = None) -> torch.Tensor:
         """addFirstFrame; T_ref_w [n, 12] f64 is frame_ref_->T_f_w_ (identity when omitted)."""
@@ -183,6 +242,7 @@ class KltHomographyInit(KltTracker):
         assert T_ref_w.dtype == torch.float64 and tuple(T_ref_w.shape) == (n, 12)
         self.T_ref_w = T_ref_w.contiguous()
         self.out = None
+        self.result = None
         return res
 
     def add_second_frame(self, store: PyramidStore, slots: torch.Tensor) -> torch.Tensor:
@@ -196,7 +256,31 @@ class KltHomographyInit(KltTracker):
         if self.out is None or self.out["inlier"].shape != (n, m):
             self.out = homography_outputs(n, m, store.device)
         homography_init(self.cam, self.f_ref, self.f_cur, status, self.px_ref, self.px_cur, self.T_ref_w, self.homography_params, self.out)
-        return torch.where(tracked, self.out["result"], gate)
+        self.result = torch.where(tracked, self.out["result"], gate)
+        return self.result
+
+    def first_map(self, store: PyramidStore, slots: torch.Tensor, frame_index: torch.Tensor | None = None, batch_id: int = 1,
+                  out: FirstMap | None = None) -> FirstMap:
+        """What processSecondFrame does with the SUCCESS of add_second_frame (frame_handler_mono.cpp:103-127), for every
+        sequence: the map, the features and key points of both keyframes, the scene depth and K1's inputs
+        (svo_hip_first_map); FAST on the free cells of `slots` (the current frames); a seed per new corner
+        (svo_hip_initialize_seeds with depth_mean and 0.5 * depth_min, as addKeyframe is called).  frame_index [n] i32 is
+        what the new features' `frame` holds (the sequence number when omitted), batch_id the value of
+        Seed::batch_counter after its increment.  `out`: a FirstMap of an earlier call to write into (HIP graphs).
+        Sequences without SUCCESS get an empty map; their seeds come from a scene depth of 0.  Everything is enqueued on
+        the current stream; nothing is read back."""
+        if self.out is None:
+            raise capi.SvoHipError("add_second_frame has not been called")
+        det = self.detector
+        fm = first_map(self.cam, self.result, self.out["point_ok"], self.out["point_w"], self.px_ref, self.px_cur, self.f_ref,
+                       self.f_cur, self.T_ref_w, self.out["T_cur_w"], det.cell_size, det.grid_n_cols, det.grid_n_rows, out)
+        xy, level, score = det.detect(store, slots, self.min_corner_score, fm.occupancy)
+        if frame_index is None:
+            frame_index = torch.arange(slots.shape[0], dtype=torch.int32, device=store.device)
+        reuse = (fm.seed_ftr, fm.seeds, fm.n_seeds) if fm.seeds is not None else None
+        fm.seed_ftr, fm.seeds, fm.n_seeds = DepthFilter.initialize_seeds(self.cam, xy, level, score, self.min_corner_score, frame_index,
+                                                                         fm.depth_mean, fm.depth_min * 0.5, batch_id, out=reuse)
+        return fm
 
     # what the reference's members hold after addSecondFrame, for every sequence
     T_cur_from_ref = property(lambda self: self.out["T_cur_from_ref"])   # [n, 12]

@@ -360,6 +360,40 @@ class DepthFilter:
         return status, xyz, px, state
 
     @staticmethod
+    def initialize_seeds(cam, corner_xy, corner_level, corner_score, detection_threshold: float, frame_index, depth_mean, depth_min,
+                         batch_id: int, seed_stride: int | None = None, out=None):
+        """DepthFilter::initializeSeeds after detect, for n keyframes (svo_hip_initialize_seeds): corner_xy [n, cells, 2] /
+        corner_level [n, cells] i32 and corner_score [n, cells] f32 are FastDetector.detect's, frame_index [n] i32 goes into
+        the new features' `frame`, depth_mean / depth_min [n] f64 are addKeyframe's arguments (the minimum already halved),
+        batch_id is Seed::batch_counter after its increment.  Returns (FeatureSet, SeedSet, n_seeds [n] i32) with columns
+        [n, seed_stride]: records 0 .. n_seeds - 1 of a row in cell order, zeros behind them.  out: that triple to reuse."""
+        lib = capi.load()
+        n, cells = corner_score.shape
+        stride = cells if seed_stride is None else int(seed_stride)
+        dev = corner_score.device
+        _chk(corner_xy, torch.int32); _chk(corner_level, torch.int32); _chk(corner_score, torch.float32)
+        _chk(frame_index, torch.int32); _chk(depth_mean, torch.float64); _chk(depth_min, torch.float64)
+        assert tuple(corner_xy.shape) == (n, cells, 2) and tuple(corner_level.shape) == (n, cells)
+        assert frame_index.shape == depth_mean.shape == depth_min.shape == (n,)
+        if out is not None:
+            ftr, seeds, n_seeds = out
+            assert tuple(seeds.mu.shape) == (n, stride)
+        else:
+            z = lambda dt, *tail: torch.zeros(n, stride, *tail, dtype=dt, device=dev)
+            ftr = FeatureSet(z(torch.int32), z(torch.int32), z(torch.float64, 2), z(torch.float64, 3), z(torch.uint8), z(torch.float64, 2))
+            seeds = SeedSet(z(torch.float32), z(torch.float32), z(torch.float32), z(torch.float32), z(torch.float32), z(torch.int32))
+            n_seeds = torch.zeros(n, dtype=torch.int32, device=dev)
+        fs, ss = ftr.struct(), seeds.struct()
+        o = capi.SeedInitOut(_chk(n_seeds, torch.int32).data_ptr(), fs.d_frame, fs.d_level, fs.d_type, fs.d_px, fs.d_f, fs.d_grad,
+                             ss.d_a, ss.d_b, ss.d_mu, ss.d_z_range, ss.d_sigma2, ss.d_batch_id)
+        c = capi.camera(cam)
+        capi.check(lib.svo_hip_initialize_seeds(C.byref(c), n, cells, corner_xy.data_ptr(), corner_level.data_ptr(),
+                                                corner_score.data_ptr(), float(detection_threshold), frame_index.data_ptr(),
+                                                depth_mean.data_ptr(), depth_min.data_ptr(), int(batch_id), stride, C.byref(o),
+                                                _stream_ptr(dev)), "svo_hip_initialize_seeds")
+        return ftr, seeds, n_seeds
+
+    @staticmethod
     def seed_store_patch(slots, src_ftr: FeatureSet, src_seeds: SeedSet, store_ftr: FeatureSet, store_seeds: SeedSet):
         """svo_hip_seed_store_patch: record i of src_* goes to slot slots[i] of the store's columns."""
         lib = capi.load()

@@ -10,7 +10,13 @@ Call times are device events around one call after a warm-up, median of 10; the 
 `rocprofv3 --kernel-trace --stats` run of its own (this script started again with --traced-child); registers / scratch /
 occupancy from the compiler's resource-usage remarks.  The algorithmic f64 operation count is derived from the shapes
 (operations() below) and the kernel is placed against operations / peak vector f64 rate.  Needs an MI355X: there is no
-CPU path, and nothing is measured without one (the JSON then says "not measured")."""
+CPU path, and nothing is measured without one (the JSON then says "not measured").
+
+--step first_map times what follows the homography step instead (svo_hip_first_map and svo_hip_initialize_seeds,
+csrc/first_map.hip; the detector between them is K7's and is not timed here) on 1 x 416 and 4096 x 416 corners (the 26 x 16
+grid of a 752 x 480 image, about 260 map points and 170 new corners per sequence) and writes profiles/first_map_bench.json:
+the same device events, the two kernels' own times from the same kind of rocprofv3 run, and the bytes the step moves, from
+the shapes, against the HBM rate."""
 from __future__ import annotations
 
 import argparse
@@ -115,6 +121,128 @@ def traced_kernel_ms(args):
     return {"error": "the kernel is not in the trace"}
 
 
+# ---- the first-map step (K10) ---------------------------------------------------------------------------------------------
+PEAK_HBM_BYTES = 8.0e12   # bytes / s (MI355X specification)
+CORNERS, GRID = 416, (30, 26, 16)
+FIRST_MAP_KERNELS = ("first_map_kernel", "seed_init_kernel")
+
+
+def first_map_bytes(n_pts, cells, share=0.625):
+    """bytes one sequence moves through both kernels: every output element is written once, an input of a corner that is
+    no map point is read only as far as its flag (share = the fraction of corners that become map points)"""
+    read = 4 + n_pts + share * n_pts * (24 + 2 * 8 + 2 * 24) + 2 * 96 + 2 * share * n_pts * 2 * 8     # (the pixels twice more: key points)
+    written = 4 + n_pts * (4 + 24 + 2 * 16 + 2 * 24 + 24) + 40 + 16 + cells
+    seeds = cells * (8 + 4 + 4) + 20 + 4 + cells * (4 + 4 + 1 + 16 + 24 + 16 + 5 * 4 + 4)
+    return read + written + seeds
+
+
+def compiler_resources_first_map():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    with tempfile.TemporaryDirectory() as tmp:
+        from rpg_svo_amd.build import FLAGS
+        r = subprocess.run([hipcc, *FLAGS, "-c", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rpg_svo_amd", "csrc"),
+                            os.path.join(ROOT, "rpg_svo_amd", "csrc", "first_map.hip"), "-o", os.path.join(tmp, "fm.o"),
+                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    out = {}
+    for blk in r.stderr.split("Function Name: ")[1:]:
+        for kern in FIRST_MAP_KERNELS:
+            if kern in blk.split()[0]:
+                g = lambda key: int(re.search(key + r": (\d+)", blk).group(1))
+                out[kern] = {"vgprs": g("VGPRs"), "agprs": g("AGPRs"), "sgprs": g("TotalSGPRs"), "scratch_bytes_per_lane": g(r"ScratchSize \[bytes/lane\]"),
+                             "occupancy_waves_per_simd": g(r"Occupancy \[waves/SIMD\]"), "lds_bytes_per_block": g(r"LDS Size \[bytes/block\]")}
+    return out or "not measured"
+
+
+def time_first_map(dev, n_seq, steps, warmup):
+    import numpy as np
+    import torch
+    import first_map_cases as cases
+    from rpg_svo_amd import initialization as init
+    from rpg_svo_amd.tracking import DepthFilter
+    cam = cases.camera(752, 480)
+    distinct = min(DISTINCT, n_seq)
+    b = cases._batch("bench", [cases.make_seq(cam, 7000 + k, CORNERS, 260) for k in range(distinct)], GRID[0])
+    assert b.grid == GRID
+    reps = -(-n_seq // distinct)
+    tile = lambda v: torch.from_numpy(np.tile(v, (reps,) + (1,) * (v.ndim - 1))[:n_seq].copy()).to(dev)
+    inp = [tile(v) for v in cases.inputs(b).values()]
+    c = cases.make_corners(7100, distinct, CORNERS, 0.4, cam)
+    corners = [tile(v) for v in (c.xy, c.level, c.score)]
+    frame_index = torch.arange(n_seq, dtype=torch.int32, device=dev)
+    fm, seeds = None, None
+    times = {"first_map": [], "initialize_seeds": [], "both": []}
+    for i in range(warmup + steps):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        fm = init.first_map(cam, *inp, *GRID, fm)
+        e[1].record()
+        seeds = DepthFilter.initialize_seeds(cam, *corners, c.threshold, frame_index, fm.depth_mean, fm.depth_min, 1, out=seeds)
+        e[2].record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            times["first_map"].append(e[0].elapsed_time(e[1]))
+            times["initialize_seeds"].append(e[1].elapsed_time(e[2]))
+            times["both"].append(e[0].elapsed_time(e[2]))
+    res = {"sequences": n_seq, "corners": CORNERS, "cells": CORNERS, "steps": steps, "mean_points": float(fm.n_points.float().mean().item()),
+           "mean_seeds": float(seeds[2].float().mean().item()), "bytes_per_sequence": first_map_bytes(CORNERS, CORNERS)}
+    for k, v in times.items():
+        v.sort()
+        res[k] = {"call_ms_median": v[len(v) // 2], "call_ms_min": v[0], "call_ms_max": v[-1]}
+    res["sequences_per_s"] = n_seq / (res["both"]["call_ms_median"] * 1e-3)
+    return res
+
+
+def traced_first_map_ms(args):
+    """Kernel times of the replay shape from rocprofv3's kernel trace, in a run of its own."""
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    out = tempfile.mkdtemp(prefix="first_map_trace_", dir=os.path.join(ROOT, "build"))
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "trace", "--", sys.executable,
+           os.path.abspath(__file__), "--step", "first_map", "--traced-child", "--pairs", str(args.pairs)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    files = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
+    if r.returncode != 0 or not files:
+        return {"error": f"rocprofv3 exit {r.returncode}: {r.stderr[-400:]}"}
+    res = {}
+    for row in csv.DictReader(open(files[0])):
+        for kern in FIRST_MAP_KERNELS:
+            if kern in row.get("Name", ""):
+                res[kern] = {"calls": int(row["Calls"]), "average_ms": float(row["AverageNs"]) * 1e-6, "min_ms": float(row["MinNs"]) * 1e-6,
+                             "max_ms": float(row["MaxNs"]) * 1e-6}
+    return res or {"error": "the kernels are not in the trace"}
+
+
+def main_first_map(args):
+    import torch
+    out = args.out or os.path.join(ROOT, "profiles", "first_map_bench.json")
+    if not torch.cuda.is_available():
+        res = {"device": "not measured", "single_sequence": "not measured", "replay_batch": "not measured", "rocprofv3": "not measured",
+               "compiler": "not measured" if args.no_compiler else compiler_resources_first_map(),
+               "bytes_per_sequence": first_map_bytes(CORNERS, CORNERS), "note": "no MI355X was available: nothing here is measured without one"}
+    else:
+        dev = torch.device("cuda:0")
+        if args.traced_child:
+            time_first_map(dev, args.pairs, 3, 1)
+            return
+        res = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("SVO_HIP_LIB", "in-tree")}
+        res["single_sequence"] = time_first_map(dev, 1, max(args.steps, 10), 5)
+        res["single_sequence"]["note"] = "one workgroup per kernel: launch-bound"
+        res["replay_batch"] = time_first_map(dev, args.pairs, args.steps, args.warmup)
+        res["compiler"] = "not measured" if args.no_compiler else compiler_resources_first_map()
+        res["rocprofv3"] = "not measured" if args.no_trace else traced_first_map_ms(args)
+        kern = sum(v["average_ms"] for v in res["rocprofv3"].values()) if isinstance(res["rocprofv3"], dict) and "error" not in res["rocprofv3"] else None
+        t_ms = kern if kern else res["replay_batch"]["both"]["call_ms_median"]
+        nbytes = res["replay_batch"]["bytes_per_sequence"] * args.pairs
+        res["hbm_bound"] = {"time_basis": "rocprofv3 kernel times, summed" if kern else "device events", "time_ms": t_ms, "bytes": nbytes,
+                            "peak_bytes_per_s": PEAK_HBM_BYTES, "least_ms_by_bytes": nbytes / PEAK_HBM_BYTES * 1e3,
+                            "achieved_bytes_per_s": nbytes / (t_ms * 1e-3), "share_of_bound": nbytes / PEAK_HBM_BYTES * 1e3 / t_ms,
+                            "klt_track_ms_same_batch": KLT_TRACK_MS, "share_of_klt_track": t_ms / KLT_TRACK_MS}
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--pairs", type=int, default=4096)
@@ -123,8 +251,12 @@ def main():
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--no-compiler", action="store_true", help="skip the compile that reports registers, scratch and occupancy")
     ap.add_argument("--traced-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "homography_bench.json"))
+    ap.add_argument("--step", choices=("homography", "first_map"), default="homography", help="which step of the bootstrap to time")
+    ap.add_argument("--out", default=None, help="default: profiles/homography_bench.json or profiles/first_map_bench.json")
     args = ap.parse_args()
+    if args.step == "first_map":
+        return main_first_map(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "homography_bench.json")
     import torch
     if not torch.cuda.is_available():
         res = {"device": "not measured", "single_pair": "not measured", "replay_batch": "not measured", "rocprofv3": "not measured",
