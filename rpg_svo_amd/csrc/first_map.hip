@@ -9,7 +9,7 @@
 // tests/first_map_checker.py restates them in sequential numpy loops.
 //
 //   first_map_kernel   one workgroup of 256 work-items per sequence.  The point_ok corners are compacted in index
-//                      order (__ballot + popcount per wave, the wave counts through LDS, as K9 does); rank -> corner
+//                      order (block_select.h's block_compact_step, which K9 uses too); rank -> corner
 //                      index and the depth of every rank stay in LDS (12 KB).  One work-item per rank copies the map
 //                      point and its two features and forms its depth, xyz_ref and grid cell.  The ten key points
 //                      (five per view) and the minimum depth are arg-max / arg-min reductions on integers: the value
@@ -17,10 +17,11 @@
 //                      the winning key through an LDS atomicMin -- "strictly better replaces" of the sequential scan
 //                      is "the best value, ties to the smallest rank".  No floating-point atomics: the same call gives
 //                      the same bits, and so do identical sequences wherever they stand in the batch.  The median
-//                      depth is klt_summarize_kernel's rank counting.
+//                      depth is block_select.h's block_rank_select.
 //   seed_init_kernel   one workgroup of 256 per keyframe: the cells with a corner are compacted in cell order, in blocks
 //                      of 256 cells with a running offset; one work-item per new seed.
 #pragma clang fp contract(off)
+#include "block_select.h"
 #include "capi_common.h"
 #include "track_math.h"
 
@@ -120,16 +121,8 @@ __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArg
   for (int c0 = 0; c0 < n_pts; c0 += FM_THREADS) {
     const int i = c0 + t;
     const bool on = success && i < n_pts && a.point_ok[base + (i < n_pts ? i : 0)] != 0;
-    const unsigned long long mask = __ballot(on);
-    const int lane = t & 63, w = t >> 6;
-    __syncthreads();
-    if (lane == 0) s_wcnt[w] = (int)__popcll(mask);
-    __syncthreads();
-    int before = m;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) before += k < w ? s_wcnt[k] : 0;
-    if (on) s_idx[before + (int)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-    m += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+    const int j = block_compact_step<FM_THREADS / 64>(on, t, s_wcnt, m);
+    if (on) s_idx[j] = i;
   }
   __syncthreads();  // (s_idx, the initial keys and the zeroed occupancy are in place)
 
@@ -220,7 +213,7 @@ __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArg
   }
   __syncthreads();
 
-  // ---- the smallest rank with that value; the median depth by rank counting --------------------------------------------
+  // ---- the smallest rank with that value; the median depth -----------------------------------------------------------------
   for (int j = t; j < m; j += FM_THREADS) {
     const size_t gi = base + s_idx[j];
 #pragma unroll
@@ -231,14 +224,9 @@ __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArg
       for (int k = 0; k < 5; ++k)
         if (kv.member[k] && !kv.nan[k] && kv.key[k] == s_key[5 * v + k]) atomicMin(&s_rank[5 * v + k], j);
     }
-    // vk::getMedian: the value of rank m / 2 in ascending order (ties by rank: equal values are the same value)
-    const double z = s_z[j];
-    if (z != z) continue;
-    int rank = 0;
-    for (int k = 0; k < m; ++k)
-      if (s_z[k] < z || (s_z[k] == z && k < j)) ++rank;
-    if (rank == m / 2) s_med = z;
   }
+  // vk::getMedian: rank m / 2 of the m depths; a NaN is never smaller or equal, so it has no rank and adds to none
+  block_rank_select<FM_THREADS>(s_z, m, m / 2, t, [&](int j) { return s_z[j] == s_z[j]; }, &s_med);
   __syncthreads();
 
   if (t < FM_KEYS) {
@@ -282,16 +270,9 @@ __global__ void __launch_bounds__(FM_THREADS) seed_init_kernel(const SeedInitArg
   for (int c0 = 0; c0 < a.n_cells; c0 += FM_THREADS) {
     const int c = c0 + t;
     const bool on = c < a.n_cells && (double)a.corner_score[in0 + (c < a.n_cells ? c : 0)] > a.detection_threshold;
-    const unsigned long long mask = __ballot(on);
-    const int lane = t & 63, w = t >> 6;
-    __syncthreads();
-    if (lane == 0) s_wcnt[w] = (int)__popcll(mask);
-    __syncthreads();
-    int before = n;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) before += k < w ? s_wcnt[k] : 0;
+    const int slot = block_compact_step<FM_THREADS / 64>(on, t, s_wcnt, n);
     if (on) {
-      const size_t s = out0 + before + (int)__popcll(mask & ((1ull << lane) - 1ull));  // at most c: inside the frame's stride
+      const size_t s = out0 + slot;  // at most c: inside the frame's stride
       const double px[2] = {(double)a.corner_xy[2 * (in0 + c)], (double)a.corner_xy[2 * (in0 + c) + 1]};
       double f[3];
       cam2world(a.cam, px[0], px[1], f);  // Feature(frame, px, level), feature.h:42-50
@@ -314,7 +295,6 @@ __global__ void __launch_bounds__(FM_THREADS) seed_init_kernel(const SeedInitArg
       o.d_sigma2[s] = sigma2;
       o.d_batch_id[s] = a.batch_id;
     }
-    n += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
   }
   if (t == 0) o.d_n_seeds[frame] = n;
   for (int j = n + t; j < a.seed_stride; j += FM_THREADS) {

@@ -17,6 +17,7 @@
 //                           barrier or an exchange is taken by the whole workgroup.  Triangulation and the map
 //                           points are one lane per point.
 #pragma clang fp contract(off)
+#include "block_select.h"
 #include "capi_common.h"
 #include "track_math.h"
 #include "wave_reduce.h"
@@ -459,16 +460,8 @@ __global__ void __launch_bounds__(HI_THREADS) homography_init_kernel(const HomAr
   for (int c0 = 0; c0 < n_pts; c0 += HI_THREADS) {
     const int i = c0 + t;
     const bool on = i < n_pts && a.status[base + (i < n_pts ? i : 0)] != 0;
-    const unsigned long long mask = __ballot(on);
-    const int lane = t & 63, w = t >> 6;
-    __syncthreads();
-    if (lane == 0) s_wcnt[w] = (int)__popcll(mask);
-    __syncthreads();
-    int before = m;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) before += k < w ? s_wcnt[k] : 0;
+    const int j = block_compact_step<HI_THREADS / 64>(on, t, s_wcnt, m);
     if (on) {
-      const int j = before + (int)__popcll(mask & ((1ull << lane) - 1ull));
       const double* fr = a.f_ref + 3 * (base + i);
       const double* fc = a.f_cur + 3 * (base + i);
       s_uv[4 * j] = fr[0] / fr[2];
@@ -477,7 +470,6 @@ __global__ void __launch_bounds__(HI_THREADS) homography_init_kernel(const HomAr
       s_uv[4 * j + 3] = fc[1] / fc[2];
       s_idx[j] = i;
     }
-    m += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
   }
   __syncthreads();
   if (m < 4) return;  // NO_MODEL (workgroup-uniform)
@@ -676,15 +668,8 @@ __global__ void __launch_bounds__(HI_THREADS) homography_init_kernel(const HomAr
   if (n_in < a.p.min_inliers || n_in == 0) return;  // FAILURE
 
   // ---- 7. scale and map -----------------------------------------------------------------------------------------------------------
-  // vk::getMedian: the value of rank n / 2 (klt_summarize_kernel's rank counting); exactly one rank matches
-  for (int j = t; j < m; j += HI_THREADS) {
-    if (!s_flag[j]) continue;
-    const double z = s_z[j];
-    int rank = 0;
-    for (int k = 0; k < m; ++k)
-      if (s_flag[k] && (s_z[k] < z || (s_z[k] == z && k < j))) ++rank;
-    if (rank == n_in / 2) s_med = z;
-  }
+  // vk::getMedian of the n_in > 0 inlier depths: exactly one rank matches
+  block_rank_select<HI_THREADS>(s_z, m, n_in / 2, t, [&](int j) { return s_flag[j] != 0; }, &s_med);
   __syncthreads();
   const double depth_median = s_med;
   const double scale = a.p.map_scale / depth_median;

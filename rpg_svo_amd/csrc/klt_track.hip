@@ -19,8 +19,10 @@
 //                         then wave_reduce.h's exchange tree: a fixed order, the same bits on every run.  Every
 //                         decision is taken on wave-uniform values, so the wave never diverges on control flow.
 //   klt_summarize_kernel  one workgroup per pair: bearing and disparity per tracked point, their number, and the median
-//                         disparity by rank counting (the element of rank n / 2 is a value, whatever algorithm finds it).
+//                         disparity by block_select.h's rank counting (the element of rank n / 2 is a value, whatever
+//                         algorithm finds it).
 #pragma clang fp contract(off)
+#include "block_select.h"
 #include "capi_common.h"
 #include "track_math.h"
 #include "wave_reduce.h"
@@ -302,15 +304,8 @@ __global__ void __launch_bounds__(256) klt_summarize_kernel(const KltSumArgs a) 
     a.n_tracked[pair] = n;
     if (n == 0) a.median[pair] = 0.0;
   }
-  // vk::getMedian: nth_element at n / 2 -- the value of that rank (ties broken by index: equal values are the same value)
-  for (int i = t; i < a.n_pts; i += 256) {
-    if (!s_on[i]) continue;
-    const double d = s_d[i];
-    int rank = 0;
-    for (int j = 0; j < a.n_pts; ++j)
-      if (s_on[j] && (s_d[j] < d || (s_d[j] == d && j < i))) ++rank;
-    if (rank == n / 2) a.median[pair] = d;
-  }
+  // vk::getMedian: nth_element at n / 2 -- the value of that rank among the tracked points
+  block_rank_select<256>(s_d, a.n_pts, n / 2, t, [&](int j) { return s_on[j] != 0; }, &a.median[pair]);
 }
 
 }  // namespace

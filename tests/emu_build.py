@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE.  The host-emulated build of the C-ABI library: the .hip translation units of rpg_svo_amd/csrc compiled by
 ROCm's clang++ as plain C++ through tests/host/hip_emu.h (work-items as fibers, barriers, LDS, cross-lane rendezvous) and
 linked into build/emu/libsvo_hip_emulated[_<defines>][_<sanitizer>].so: ONE library with every kernel family, the entry points of
-libsvo_hip.so's kernel files on host memory; no timing."""
+libsvo_hip.so's kernel files on host memory; no timing.  Also K10's stand-alone sanitizer program, compiled with the same flags."""
 import ctypes as C
 import glob
 import os
@@ -11,7 +11,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNITS = ("common", "pyramid", "map_mirror", "matcher", "feature_align", "depth_filter", "sparse_align", "sparse_align_wave",
-         "pose_optimizer_wave", "pose_optimizer", "point_optimizer", "fast_detect", "klt_track", "homography_init")
+         "pose_optimizer_wave", "pose_optimizer", "point_optimizer", "fast_detect", "klt_track", "homography_init", "first_map")
 
 
 # Compile-time variants of the library the emulated parity tests run on besides the default build (round 4 queued ten of
@@ -77,6 +77,20 @@ def build_race_probe():
     return lib
 
 
+def _kernel_cxxflags(defines):
+    """THE compile flags of the kernel files for the host: the objects of build_emulated and the stand-alone sanitizer program"""
+    return ["-std=c++17", "-O1", "-ffp-contract=off", "-fno-math-errno", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-pass-failed",
+            "-Wno-unused-function", "-Wno-unused-variable", *[f"-D{d}" for d in defines], "-I", os.path.join(ROOT, "include"),
+            "-I", os.path.join(ROOT, "rpg_svo_amd", "csrc"), "-I", os.path.join(ROOT, "tests", "host")]
+
+
+def _kernel_deps():
+    """what every emulated translation unit is rebuilt after, besides its own emu_tu_*.cpp"""
+    csrc = os.path.join(ROOT, "rpg_svo_amd", "csrc")
+    return glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + \
+        [os.path.join(ROOT, "include", "svo_hip.h"), os.path.join(ROOT, "tests", "host", "hip_emu.h")]
+
+
 def build_emulated(defines=()):
     # SVO_EMU_EXTRA_DEFINES="A B": added to every emulated build of the run (e.g. the whole round-5 queue on the default tests)
     from rpg_svo_amd.build import DEFAULT_DEFINES   # (the default library's own flags: the emulated default build has them too)
@@ -92,13 +106,10 @@ def build_emulated(defines=()):
     lib_path = os.path.join(ROOT, "build", "emu", f"libsvo_hip_emulated{tag}.so")
     objdir = os.path.join(ROOT, "build", "emu", f"obj{tag}")
     os.makedirs(objdir, exist_ok=True)
-    csrc = os.path.join(ROOT, "rpg_svo_amd", "csrc")
     cxx = _cxx()
     if not os.path.exists(cxx):
         pytest.skip("no ROCm clang++ to compile the kernels for the host")
-    deps = glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + \
-        [os.path.join(ROOT, "include", "svo_hip.h"), os.path.join(ROOT, "tests", "host", "hip_emu.h")]
-    newest = max(os.path.getmtime(d) for d in deps)
+    newest = max(os.path.getmtime(d) for d in _kernel_deps())
     # (a change of flags rebuilds too: the object directory remembers what it was compiled with)
     stamp, flags_now = os.path.join(objdir, "flags.txt"), " ".join([*san_flags, *defines, "-O1"])
     if not os.path.exists(stamp) or open(stamp).read() != flags_now:
@@ -111,10 +122,7 @@ def build_emulated(defines=()):
         obj = os.path.join(objdir, f"{u}.o")
         objs.append(obj)
         if not os.path.exists(obj) or os.path.getmtime(obj) < max(newest, os.path.getmtime(src)):
-            todo.append([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-fno-math-errno", "-fPIC", "-c", "-Wall", "-Wno-unknown-pragmas",
-                         "-Wno-pass-failed", "-Wno-unused-function", "-Wno-unused-variable", *san_flags,
-                         *[f"-D{d}" for d in defines], "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                         "-I", os.path.join(ROOT, "tests", "host"), src, "-o", obj])
+            todo.append([cxx, *_kernel_cxxflags(defines), *san_flags, "-c", src, "-o", obj])
     if todo:  # the translation units in parallel: a cold build of one variant set takes about as long as its slowest unit
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=min(8, len(todo))) as ex:
@@ -123,3 +131,19 @@ def build_emulated(defines=()):
         subprocess.run([cxx, "-shared", *san_flags, "-o", lib_path, *objs], check=True)
     lib = C.CDLL(lib_path)
     return lib
+
+
+def build_first_map_asan_program():
+    """-> the path of build/emu/first_map_asan: K10's emulated units and tests/host/first_map_asan_main.cpp, one executable
+    instrumented with AddressSanitizer and UndefinedBehaviorSanitizer (a program of its own: nothing is loaded into Python)"""
+    from rpg_svo_amd.build import DEFAULT_DEFINES
+    cxx = _cxx()
+    if not os.path.exists(cxx):
+        pytest.skip("no ROCm clang++ to compile the kernels for the host")
+    exe = os.path.join(ROOT, "build", "emu", "first_map_asan")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    srcs = [os.path.join(ROOT, "tests", "host", f) for f in ("emu_tu_common.cpp", "emu_tu_first_map.cpp", "first_map_asan_main.cpp")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in [*srcs, *_kernel_deps(), os.path.abspath(__file__)]):
+        subprocess.run([cxx, *_kernel_cxxflags(DEFAULT_DEFINES), "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-fno-sanitize=vptr,function", "-fno-omit-frame-pointer", "-g", *srcs, "-o", exe], check=True)
+    return exe

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: rpg_svo_amd/csrc/first_map.hip compiled for the host (tests/host/hip_emu.h); tests/emu_build_first_map.py
-// links it with emu_tu_common.cpp into a library of its own.
+// TEST INFRASTRUCTURE: rpg_svo_amd/csrc/first_map.hip compiled for the host (tests/host/hip_emu.h); a unit of the emulated
+// library, and with emu_tu_common.cpp of the stand-alone sanitizer program (tests/emu_build.py builds both).
 #include "hip_emu.h"
 #include "../../rpg_svo_amd/csrc/first_map.hip"

@@ -2,7 +2,7 @@
 // host-emulated form (emu_tu_first_map.cpp, emu_tu_common.cpp) on heap buffers of exactly the sizes the C ABI asks for: 257
 // corners in three sequences (two chunks of the compaction loop, a failed sequence in the middle, pixels that are NaN,
 // negative and beyond the grid) and 1040 cells in two keyframes (five blocks of the running offset).  Built with
-// -fsanitize=address,undefined by tests/emu_build_first_map.py: a load or store outside a buffer, or undefined behaviour in
+// -fsanitize=address,undefined by tests/emu_build.py: a load or store outside a buffer, or undefined behaviour in
 // the kernels, stops it with a report and a non-zero exit status.  Exits 0 when both calls return SVO_HIP_OK with the counts
 // the inputs were made for.
 #include <cmath>

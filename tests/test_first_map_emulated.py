@@ -1,5 +1,5 @@
 """svo_hip_first_map and svo_hip_initialize_seeds (K10, csrc/first_map.hip) of the host-emulated build
-(tests/emu_build_first_map.py: the kernels compiled for the CPU through tests/host/hip_emu.h, one fiber per work-item, the
+(tests/emu_build.py: the kernels compiled for the CPU through tests/host/hip_emu.h, one fiber per work-item, the
 LDS atomics as host atomics) on the cases of tests/first_map_cases.py against the sequential checker
 (tests/first_map_checker.py): EVERY output bit for bit.  Every output buffer lies between two guard bands and starts
 poisoned: whatever the entry defines it must write, and nothing else.
@@ -20,8 +20,11 @@ GUARD = 64          # elements of 0xA5 bytes on either side of every output
 
 @pytest.fixture(scope="module")
 def emu():
-    from emu_build_first_map import build_first_map_emulated
-    return build_first_map_emulated()
+    from emu_build import build_emulated
+    lib = build_emulated(())   # (a CDLL object of this module's own; the cases pass addresses as ints, which need the argtypes)
+    for name in ("svo_hip_first_map", "svo_hip_initialize_seeds"):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = capi.PROTOTYPES[name]
+    return lib
 
 
 class Guarded:
