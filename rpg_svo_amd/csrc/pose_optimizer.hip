@@ -433,7 +433,7 @@ static int pose_optimize_impl(PoseMode mode, const svo_hip_camera* cam, int B, c
   w.stats = d_stats;
   w.ran = d_ran;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == POSE_ORDERED || n_stride > svo_track::POSE_WAVE_MAX_STRIDE)  // (more than 4 observations per lane: ordered kernel)
+  if (mode == POSE_ORDERED || n_stride > svo_track::POSE_WAVE_MAX_STRIDE)  // (more than 4 trips of 64 observations: ordered kernel)
     return launch_ordered(w, 0, s);
   const int rc = svo_track::launch_pose_wave(w, s);
   if (rc != SVO_HIP_OK || mode == POSE_WAVE_DEFERRED) return rc;

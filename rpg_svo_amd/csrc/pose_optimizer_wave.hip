@@ -1,5 +1,5 @@
 // pose_optimizer_wave.hip -- K4 (default form): batched pose_optimizer::optimizeGaussNewton, one
-// WAVE per frame, several frames per workgroup, no workgroup barrier and no LDS.
+// WAVE per frame, several frames per workgroup, no workgroup barrier.
 //
 // Replaces svo::pose_optimizer::optimizeGaussNewton (svo/src/pose_optimizer.cpp:28-161) to a
 // stated tolerance (pose within 1e-9 of the reference, SE(3) log-map norm; pruning decisions on
@@ -7,18 +7,29 @@
 // reference's summation order (pose_optimizer.hip, svo_hip_pose_optimize_ordered) stays as the
 // checker; this kernel is what the pipeline runs:
 //
-//   * a lane keeps up to 4 observations (point, normalised measurement, level scale) in
-//     registers for the whole call: nothing is re-read from HBM between Gauss-Newton iterations;
-//   * the 27 non-zero f64 sums of an iteration (20 entries of A -- A(0,1) is identically zero,
-//     b[6], chi2) are accumulated per lane and reduced over the wave with a TRANSPOSING
+//   * a wave reads its row once (the flag first; f, pos, level of live slots only) and writes the LIVE observations side by
+//     side, in index order (position = ballot + popcount of the lanes below: nothing depends on timing), into its own block
+//     of the workgroup's dynamic LDS: px py pz ux uy as f64, the level scale as f32, the slot it came from as u8 -- 45 bytes
+//     per observation, structure of arrays over n_stride (rounded up to 8) positions, 9 000 bytes per wave and 36 000 per
+//     workgroup at n_stride = 200, so that four workgroups fit a CU.  Nothing is re-read from HBM between Gauss-Newton
+//     iterations, and the observations cost no registers: 126 VGPRs, four waves per SIMD (occupancy is what hides the f64
+//     dependency chains of the solve: there is no memory access in the loop to overlap them with);
+//   * an iteration walks the block in ceil(n_live / 64) trips -- a runtime loop, so a frame of 172 live observations in a
+//     row of 200 pays three trips, not four; a lane past n_live in the last trip reads the last live record again and counts
+//     with weight 0.  The two passes around the loop (MAD scale / initial median, pruning / final median) read the same block;
+//     pruning clears has_point at the slot the record came from.  The block is the wave's alone: same-wave DS operations
+//     execute in order, SVO_WAVE_LDS_FENCE keeps the compiler from moving the reads above the stores, and there is no barrier;
+//   * the 25 distinct non-zero f64 sums of an iteration (18 entries of A -- A(0,1) is identically zero, A(1,1) is A(0,0) and
+//     A(1,4) is -A(0,3) bit for bit --, b[6], chi2) are accumulated per lane and reduced over the wave with a TRANSPOSING
 //     butterfly (v_permlane32_swap / v_permlane16_swap / DPP): 32 f64 additions instead of
-//     27 x 6, no LDS round trip, no ordered chain;
+//     25 x 6, no LDS round trip, no ordered chain;
 //   * the 6x6 solve, SE3::exp(dT)*T and the stop / rollback rules run redundantly in every lane
 //     on wave-uniform values (readlane broadcasts): no serial lane, no barrier.  The solve is an
 //     unpivoted LDL^T; only when a pivot collapses (rank-deficient systems of a handful of
 //     observations) the wave falls back to Eigen's pivoted algorithm, as the ordered kernel uses;
 //   * MAD scale and the two reported medians are exact order statistics found by a bitwise
-//     radix select over the wave (ballot + popcount per bit), not by O(n^2) rank counting.
+//     radix select over the wave (ballot + popcount per bit), not by O(n^2) rank counting; its keys (up to four per lane)
+//     stay in registers.
 #include "track_kernels.h"
 #include "track_math.h"
 #include "wave_reduce.h"
@@ -31,7 +42,7 @@ namespace {
 using svo_track::PoseWaveArgs;
 
 constexpr int PW_WAVES = 4;  // frames per workgroup
-constexpr int PW_MINW = 3;  // waves per SIMD asked of the register allocator (<= 168 VGPRs)
+constexpr int PW_MINW = 4;  // waves per SIMD asked of the register allocator (<= 128 VGPRs)
 constexpr double SVO_EPS = 0.0000000001;  // svo/include/svo/global.h:77
 
 
@@ -100,8 +111,9 @@ __device__ __forceinline__ double fast_sqrt(double x) {
 // ldlt6_factor (device_math.h) with the six pivot reciprocals by v_rcp_f64 + Newton.  A vanished pivot leaves LD[15 + j] = 0
 // and a column that means nothing (v * 0: ldlt6_factor keeps v): the only caller hands such a frame to the ordered kernel
 // (pivots_ok) before anything reads the factor -- fifteen selects per Gauss-Newton iteration less.
-// (Skipping the fourth observation slot of a frame of <= 192 observations behind a scalar branch: five more 8-byte spills,
-// 0.232 -> 0.235 ms, profiles/r06ag_*.)
+// (Skipping the fourth observation slot of a frame of <= 192 observations behind a scalar branch, with the observations in
+// registers: five more 8-byte spills, 0.232 -> 0.235 ms, profiles/r06ag_*.  With the observations in LDS the trips are a
+// runtime loop and the fourth one is simply not made.)
 __device__ __forceinline__ void ldlt6_factor_fast(const double H[21], double LD[21]) {
   double d[6];
 #pragma unroll
@@ -234,48 +246,101 @@ __device__ __forceinline__ bool pivots_ok(const double A[21], const double LD[21
 template <int J>
 __device__ __forceinline__ double bcast(double v) { return readlane_f64<2 * J>(v); }
 
-// The 27 sums in reduction order:
+// One observation as the passes read it back from the wave's LDS block
+struct PwObs {
+  double px, py, pz, ux, uy, k;
+};
+
+// The wave's private block of the workgroup's dynamic LDS, structure of arrays over `cap` positions (cap = n_stride rounded up
+// to 8, so that every array starts 8-byte aligned): px py pz ux uy as f64, the level scale as f32, the original slot as u8 --
+// 45 bytes per position.
+struct PwBlock {
+  double* d;      // [5][cap]
+  float* k;       // [cap]
+  uint8_t* slot;  // [cap]
+  int cap;
+  __device__ __forceinline__ PwObs load(int c) const {  // c: clamped by the caller
+    PwObs o;
+    o.px = d[c]; o.py = d[cap + c]; o.pz = d[2 * cap + c]; o.ux = d[3 * cap + c]; o.uy = d[4 * cap + c];
+    o.k = (double)k[c];
+    return o;
+  }
+};
+constexpr int PW_BYTES_PER_OBS = 5 * 8 + 4 + 1;
+__host__ __device__ constexpr int pw_cap(int n_stride) { return (n_stride + 7) & ~7; }
+
+// e = (u - project2d(T p)) * sqrt_inv_cov of one observation: e2 = |e|^2 (the residual of the two median passes; the
+// Gauss-Newton loop forms the same expressions and keeps the intermediates)
+__device__ __forceinline__ double pw_e2(const PwObs& o, const double R[9], const double t[3]) {
+  const double x = R[0] * o.px + R[1] * o.py + R[2] * o.pz + t[0];
+  const double y = R[3] * o.px + R[4] * o.py + R[5] * o.pz + t[1];
+  const double z = R[6] * o.px + R[7] * o.py + R[8] * o.pz + t[2];
+  const double zi = fast_rcp(z);  // (as in the iterations: the same residuals as iteration 0)
+  const double e0 = (o.ux - x * zi) * o.k, e1 = (o.uy - y * zi) * o.k;
+  return e0 * e0 + e1 * e1;
+}
+
+// rank k among the keys of the first `trips` (wave-uniform, 1..4) of kd[4]
+__device__ __forceinline__ double pw_select(const unsigned long long kd[4], int trips, int k) {
+  unsigned long long r;
+  if (trips <= 1) r = radix_select<1, unsigned long long>(kd, k, 62);
+  else if (trips == 2) r = radix_select<2, unsigned long long>(kd, k, 62);
+  else if (trips == 3) r = radix_select<3, unsigned long long>(kd, k, 62);
+  else r = radix_select<4, unsigned long long>(kd, k, 62);
+  return __longlong_as_double((long long)r);
+}
+
+// The 25 sums in reduction order (two more of the 27 non-zero entries are copies: A(1,1) is the expression of A(0,0), since
+// j11 == j00, and A(1,4) is -A(0,3) bit for bit, since j14 == -j03 and rounding to nearest is symmetric):
 //   0..4   A(0,0) A(0,2) A(0,3) A(0,4) A(0,5)
-//   5..9   A(1,1) A(1,2) A(1,3) A(1,4) A(1,5)
+//   6,7,9  A(1,2) A(1,3) A(1,5)          (5 and 8 stay zero)
 //   10..19 A(2,2) A(2,3) A(2,4) A(2,5) A(3,3) A(3,4) A(3,5) A(4,4) A(4,5) A(5,5)
 //   20..25 b[0..5]   26 chi2
-template <int NPL>
 __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(const PoseWaveArgs a) {
+  SVO_DYNAMIC_LDS(double, pw_dyn);
   const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * PW_WAVES + (threadIdx.x >> 6);
+  const int wave = threadIdx.x >> 6;
+  const int b = blockIdx.x * PW_WAVES + wave;
   if (b >= a.B) return;
-  int n = a.n[b];
+  int n = __builtin_amdgcn_readfirstlane(a.n[b]);
   n = n < 0 ? 0 : (n > a.n_stride ? a.n_stride : n);  // contract: n <= n_stride (svo_hip.h); never read past the row
   const size_t base = (size_t)b * a.n_stride;
   const double focal = fabs(a.cam.fx);
 
-  // ---- this lane's observations, resident for the whole call ---------------------------
-  double px[NPL], py[NPL], pz[NPL], ux[NPL], uy[NPL];
-  float kk[NPL];
-  bool live[NPL];
-  int n_err = 0;
-#pragma unroll
-  for (int j = 0; j < NPL; ++j) {
+  // ---- this wave's observations: the live ones, in index order, side by side in LDS for the whole call -----------
+  PwBlock blk;
+  blk.cap = pw_cap(a.n_stride);
+  blk.d = pw_dyn + (size_t)wave * (blk.cap / 8) * PW_BYTES_PER_OBS;  // (cap * 45 bytes per wave: a multiple of 8)
+  blk.k = reinterpret_cast<float*>(blk.d + 5 * blk.cap);
+  blk.slot = reinterpret_cast<uint8_t*>(blk.k + blk.cap);
+  int n_live = 0;
+  for (int j = 0; j * 64 < n; ++j) {
     const int i = j * 64 + lane;
-    live[j] = (i < n) && a.has_point[base + i] != 0;
-    px[j] = py[j] = 0.0;
-    pz[j] = 1.0;
-    ux[j] = uy[j] = 0.0;
-    kk[j] = 1.f;
-    if (live[j]) {
+    const bool live = (i < n) && a.has_point[base + i] != 0;
+    const unsigned long long m = __ballot(live);
+    if (live) {
+      // position = the number of live observations before this one; < n <= cap by construction, clamped all the same
+      const int at = n_live + __popcll(m & ((1ull << lane) - 1ull));
+      const int c = at < blk.cap ? at : blk.cap - 1;
       const double* p = a.pos + 3 * (base + i);
       const double* f = a.f + 3 * (base + i);
-      px[j] = p[0]; py[j] = p[1]; pz[j] = p[2];
-      ux[j] = f[0] / f[2];  // vk::project2d(f), once
-      uy[j] = f[1] / f[2];
-      kk[j] = pow2_inv_f32(a.level[base + i]);  // == 1.0f / (float)(1 << level), from exponent bits
+      blk.d[c] = p[0]; blk.d[blk.cap + c] = p[1]; blk.d[2 * blk.cap + c] = p[2];
+      blk.d[3 * blk.cap + c] = f[0] / f[2];  // vk::project2d(f), once
+      blk.d[4 * blk.cap + c] = f[1] / f[2];
+      blk.k[c] = pow2_inv_f32(a.level[base + i]);  // == 1.0f / (float)(1 << level), from exponent bits
+      blk.slot[c] = (uint8_t)i;
     }
-    n_err += __popcll(__ballot(live[j]));
+    n_live += __popcll(m);
   }
-  if (n_err == 0) {  // errors.empty(): return before touching anything (:57-58)
+  if (n_live == 0) {  // errors.empty(): return before touching anything (:57-58)
     if (lane == 0) a.ran[b] = 0;
     return;
   }
+  SVO_WAVE_LDS_FENCE();  // the block is this wave's alone: its DS operations execute in order, no barrier
+  // Trip t gives lane l the observation at position 64 t + l.  A lane past n_live in the last trip reads the last live
+  // record again (a valid address and finite numbers) and counts with weight 0 / key +inf: the neutral record.
+  const int last_pos = (n_live < blk.cap ? n_live : blk.cap) - 1;
+  const int trips = (n_live + 63) >> 6;
 
   // model, wave-uniform (every lane loads the same 12 doubles)
   Se3 T, T_old;
@@ -290,19 +355,17 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   // ---- error scale (:45-60) and the median of chi2_vec_init (same residuals as iteration 0) ----
   double estimated_scale, med_init;
   {
-    unsigned long long kd[NPL];
+    unsigned long long kd[4];
 #pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      const double x = R[0] * px[j] + R[1] * py[j] + R[2] * pz[j] + T.t[0];
-      const double y = R[3] * px[j] + R[4] * py[j] + R[5] * pz[j] + T.t[1];
-      const double z = R[6] * px[j] + R[7] * py[j] + R[8] * pz[j] + T.t[2];
-      const double k = (double)kk[j];
-      const double zi = fast_rcp(z);  // (as in the iterations below: the same residuals as iteration 0)
-      const double e0 = (ux[j] - x * zi) * k, e1 = (uy[j] - y * zi) * k;
-      const double e2 = e0 * e0 + e1 * e1;
-      kd[j] = live[j] ? (unsigned long long)__double_as_longlong(e2) : 0x7ff0000000000000ull;
+    for (int j = 0; j < 4; ++j) {
+      kd[j] = 0x7ff0000000000000ull;
+      if (j < trips) {
+        const int at = j * 64 + lane;
+        const double e2 = pw_e2(blk.load(at < last_pos ? at : last_pos), R, T.t);
+        if (at < n_live) kd[j] = (unsigned long long)__double_as_longlong(e2);
+      }
     }
-    med_init = __longlong_as_double((long long)radix_select<NPL, unsigned long long>(kd, n_err / 2, 62));
+    med_init = pw_select(kd, trips, n_live / 2);
     // The scale estimator's median is over errors = (float)sqrt(e2) of the same observations (:52-56), rank n / 2 as well:
     // sqrt and the conversion are monotone, so the rank-k error IS the image of the rank-k e2 -- one selection, not two
     // (equal images of different e2 are the same value).
@@ -324,32 +387,32 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     double acc[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      const double x = R[0] * px[j] + R[1] * py[j] + R[2] * pz[j] + T.t[0];
-      const double y = R[3] * px[j] + R[4] * py[j] + R[5] * pz[j] + T.t[1];
-      const double z = R[6] * px[j] + R[7] * py[j] + R[8] * pz[j] + T.t[2];
+#pragma unroll 1
+    for (int j = 0; j < trips; ++j) {  // a lane adds its observations in trip order
+      const int at = j * 64 + lane;
+      const PwObs o = blk.load(at < last_pos ? at : last_pos);
+      const double x = R[0] * o.px + R[1] * o.py + R[2] * o.pz + T.t[0];
+      const double y = R[3] * o.px + R[4] * o.py + R[5] * o.pz + T.t[1];
+      const double z = R[6] * o.px + R[7] * o.py + R[8] * o.pz + T.t[2];
       const double zi = fast_rcp(z);
       const double xn = x * zi, yn = y * zi;
-      const double k = (double)kk[j];
-      const double e0 = (ux[j] - xn) * k, e1 = (uy[j] - yn) * k;  // e *= sqrt_inv_cov
+      const double k = o.k;
+      const double e0 = (o.ux - xn) * k, e1 = (o.uy - yn) * k;  // e *= sqrt_inv_cov
       const double e2 = e0 * e0 + e1 * e1;
       const float wf = tukey_w((float)(fast_sqrt(e2) * inv_scale));
-      const double w = live[j] ? (double)wf : 0.0;
-      // Frame::jacobian_xyz2uv (frame.h:116-138), rows J0 / J1 scaled by sqrt_inv_cov
+      const double w = at < n_live ? (double)wf : 0.0;
+      // Frame::jacobian_xyz2uv (frame.h:116-138), rows J0 / J1 scaled by sqrt_inv_cov; j11 == j00, j14 == -j03
       const double j00 = -zi * k, j02 = xn * zi * k, j03 = xn * yn * k, j04 = -(1.0 + xn * xn) * k, j05 = yn * k;
-      const double j11 = -zi * k, j12 = yn * zi * k, j13 = (1.0 + yn * yn) * k, j14 = -j03, j15 = -xn * k;
+      const double j12 = yn * zi * k, j13 = (1.0 + yn * yn) * k, j14 = -j03, j15 = -xn * k;
       const double w00 = w * j00, w02 = w * j02, w03 = w * j03, w04 = w * j04, w05 = w * j05;
-      const double w11 = w * j11, w12 = w * j12, w13 = w * j13, w14 = w * j14, w15 = w * j15;
+      const double w11 = w00, w12 = w * j12, w13 = w * j13, w14 = w * j14, w15 = w * j15;
       acc[0] = fma(w00, j00, acc[0]);
       acc[1] = fma(w00, j02, acc[1]);
       acc[2] = fma(w00, j03, acc[2]);
       acc[3] = fma(w00, j04, acc[3]);
       acc[4] = fma(w00, j05, acc[4]);
-      acc[5] = fma(w11, j11, acc[5]);
       acc[6] = fma(w11, j12, acc[6]);
       acc[7] = fma(w11, j13, acc[7]);
-      acc[8] = fma(w11, j14, acc[8]);
       acc[9] = fma(w11, j15, acc[9]);
       acc[10] = fma(w02, j02, fma(w12, j12, acc[10]));
       acc[11] = fma(w02, j03, fma(w12, j13, acc[11]));
@@ -372,14 +435,14 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     }
     const double tot = wave_reduce32_f64(acc, lane);
     const double s0 = bcast<0>(tot), s1 = bcast<1>(tot), s2 = bcast<2>(tot), s3 = bcast<3>(tot), s4 = bcast<4>(tot);
-    const double s5 = bcast<5>(tot), s6 = bcast<6>(tot), s7 = bcast<7>(tot), s8 = bcast<8>(tot), s9 = bcast<9>(tot);
+    const double s6 = bcast<6>(tot), s7 = bcast<7>(tot), s9 = bcast<9>(tot);
     const double s10 = bcast<10>(tot), s11 = bcast<11>(tot), s12 = bcast<12>(tot), s13 = bcast<13>(tot);
     const double s14 = bcast<14>(tot), s15 = bcast<15>(tot), s16 = bcast<16>(tot), s17 = bcast<17>(tot);
     const double s18 = bcast<18>(tot), s19 = bcast<19>(tot);
     const double bv[6] = {bcast<20>(tot), bcast<21>(tot), bcast<22>(tot), bcast<23>(tot), bcast<24>(tot), bcast<25>(tot)};
     const double new_chi2 = bcast<26>(tot);
     A[sym6(0, 0)] = s0; A[sym6(0, 1)] = 0.0; A[sym6(0, 2)] = s1; A[sym6(0, 3)] = s2; A[sym6(0, 4)] = s3; A[sym6(0, 5)] = s4;
-    A[sym6(1, 1)] = s5; A[sym6(1, 2)] = s6; A[sym6(1, 3)] = s7; A[sym6(1, 4)] = s8; A[sym6(1, 5)] = s9;
+    A[sym6(1, 1)] = s0; A[sym6(1, 2)] = s6; A[sym6(1, 3)] = s7; A[sym6(1, 4)] = -s2; A[sym6(1, 5)] = s9;
     A[sym6(2, 2)] = s10; A[sym6(2, 3)] = s11; A[sym6(2, 4)] = s12; A[sym6(2, 5)] = s13;
     A[sym6(3, 3)] = s14; A[sym6(3, 4)] = s15; A[sym6(3, 5)] = s16;
     A[sym6(4, 4)] = s17; A[sym6(4, 5)] = s18; A[sym6(5, 5)] = s19;
@@ -444,30 +507,33 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   int n_deleted = 0;
   double med_final;
   {
-    unsigned long long kd[NPL];
+    unsigned long long kd[4];
 #pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      const double x = R[0] * px[j] + R[1] * py[j] + R[2] * pz[j] + T.t[0];
-      const double y = R[3] * px[j] + R[4] * py[j] + R[5] * pz[j] + T.t[1];
-      const double z = R[6] * px[j] + R[7] * py[j] + R[8] * pz[j] + T.t[2];
-      const double k = (double)kk[j];
-      const double zi = fast_rcp(z);
-      const double e0 = (ux[j] - x * zi) * k, e1 = (uy[j] - y * zi) * k;
-      const double e2 = e0 * e0 + e1 * e1;
-      kd[j] = live[j] ? (unsigned long long)__double_as_longlong(e2) : 0x7ff0000000000000ull;
-      // e.norm() > reproj_thresh_scaled (:136) as e2 > thresh^2: the pose this kernel arrives at differs from the reference's
-      // by up to 1e-9, which moves e2 by far more than the rounding of a division or a square root -- no decision hangs on them
-      const bool prune = live[j] && e2 > reproj_thresh2;
-      if (prune) a.has_point[base + j * 64 + lane] = 0;  // (*it)->point = NULL
-      n_deleted += __popcll(__ballot(prune));
+    for (int j = 0; j < 4; ++j) {
+      kd[j] = 0x7ff0000000000000ull;
+      if (j < trips) {
+        const int at = j * 64 + lane;
+        const int c = at < last_pos ? at : last_pos;
+        const double e2 = pw_e2(blk.load(c), R, T.t);
+        const bool live = at < n_live;
+        if (live) kd[j] = (unsigned long long)__double_as_longlong(e2);
+        // e.norm() > reproj_thresh_scaled (:136) as e2 > thresh^2: the pose this kernel arrives at differs from the reference's
+        // by up to 1e-9, which moves e2 by far more than the rounding of a division or a square root -- no decision hangs on them
+        const bool prune = live && e2 > reproj_thresh2;
+        if (prune) {
+          const int slot = blk.slot[c];  // where the observation came from (< n: only such slots were stored)
+          if (slot < n) a.has_point[base + slot] = 0;  // (*it)->point = NULL
+        }
+        n_deleted += __popcll(__ballot(prune));
+      }
     }
-    med_final = __longlong_as_double((long long)radix_select<NPL, unsigned long long>(kd, n_err / 2, 62));
+    med_final = pw_select(kd, trips, n_live / 2);
   }
   if (lane == 0) {
     a.stats[4 * b + 0] = estimated_scale * focal;
     a.stats[4 * b + 1] = a.n_iter > 0 ? sqrt(med_init) * focal : 0.0;  // chi2_vec_init is empty without an iteration
     a.stats[4 * b + 2] = sqrt(med_final) * focal;
-    a.stats[4 * b + 3] = (double)(n_err - n_deleted);
+    a.stats[4 * b + 3] = (double)(n_live - n_deleted);
     a.ran[b] = 1;
   }
 }
@@ -476,13 +542,11 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
 
 namespace svo_track {
 
-// n_stride <= 256 only (4 observations per lane); the caller falls back to the ordered kernel beyond
+// n_stride <= 256 only (the radix select keeps 4 keys per lane in registers); the caller falls back to the ordered kernel beyond
 int launch_pose_wave(const PoseWaveArgs& a, hipStream_t s) {
   const int grid = (a.B + PW_WAVES - 1) / PW_WAVES;
-  const dim3 g(grid), blk(64 * PW_WAVES);
-  if (a.n_stride <= 64) hipLaunchKernelGGL(pose_opt_wave_kernel<1>, g, blk, 0, s, a);
-  else if (a.n_stride <= 128) hipLaunchKernelGGL(pose_opt_wave_kernel<2>, g, blk, 0, s, a);
-  else hipLaunchKernelGGL(pose_opt_wave_kernel<4>, g, blk, 0, s, a);
+  const size_t lds = (size_t)PW_WAVES * pw_cap(a.n_stride) * PW_BYTES_PER_OBS;  // <= 46 080 bytes
+  hipLaunchKernelGGL(pose_opt_wave_kernel, dim3(grid), dim3(64 * PW_WAVES), lds, s, a);
   return check_launch();
 }
 

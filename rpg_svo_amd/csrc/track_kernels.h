@@ -63,7 +63,7 @@ struct WarpArgs {
 };
 int launch_warp(const WarpArgs& a, hipStream_t s);
 
-// K4 (pose_optimizer_wave.hip): one wave per frame, n_stride <= 256
+// K4 (pose_optimizer_wave.hip): one wave per frame, n_stride <= 256 (dynamic LDS: 45 bytes per slot and wave)
 struct PoseWaveArgs {
   svo_hip_camera cam;
   int B;
