@@ -1,5 +1,5 @@
 // pose_optimizer_wave.hip -- K4 (default form): batched pose_optimizer::optimizeGaussNewton, one
-// WAVE per frame, several frames per workgroup, no workgroup barrier.
+// WAVE per frame, one frame per workgroup (PW_WAVES), no workgroup barrier.
 //
 // Replaces svo::pose_optimizer::optimizeGaussNewton (svo/src/pose_optimizer.cpp:28-161) to a
 // stated tolerance (pose within 1e-9 of the reference, SE(3) log-map norm; pruning decisions on
@@ -10,9 +10,10 @@
 //   * a wave reads its row once (the flag first; f, pos, level of live slots only) and writes the LIVE observations side by
 //     side, in index order (position = ballot + popcount of the lanes below: nothing depends on timing), into its own block
 //     of the workgroup's dynamic LDS: px py pz ux uy as f64, the level scale as f32, the slot it came from as u8 -- 45 bytes
-//     per observation, structure of arrays over n_stride (rounded up to 8) positions, 9 000 bytes per wave and 36 000 per
-//     workgroup at n_stride = 200, so that four workgroups fit a CU.  Nothing is re-read from HBM between Gauss-Newton
-//     iterations, and the observations cost no registers: 126 VGPRs, four waves per SIMD (occupancy is what hides the f64
+//     per observation, structure of arrays over n_stride (rounded up to 8) positions, 9 000 bytes per wave (= workgroup) at
+//     n_stride = 200, so that sixteen of them fit a CU's 160 KB, and a finished frame frees its block for the next workgroup at
+//     once (11 520 bytes and fourteen at n_stride = 256).  Nothing is re-read from HBM between Gauss-Newton
+//     iterations, and the observations cost no registers: 127 VGPRs, four waves per SIMD (occupancy is what hides the f64
 //     dependency chains of the solve: there is no memory access in the loop to overlap them with);
 //   * an iteration walks the block in ceil(n_live / 64) trips -- a runtime loop, so a frame of 172 live observations in a
 //     row of 200 pays three trips, not four; a lane past n_live in the last trip reads the last live record again and counts
@@ -41,7 +42,13 @@ namespace {
 
 using svo_track::PoseWaveArgs;
 
-constexpr int PW_WAVES = 4;  // frames per workgroup
+// Frames (= waves) per workgroup: ONE.  Nothing ties the waves of a workgroup together but the LDS, which the hardware hands
+// out per workgroup and takes back only when its LAST wave ends: with four frames per workgroup a frame that rolled back after
+// two iterations held its block until the slowest of its three neighbours was through (on the benchmark's rows E[max of 4] /
+// E[T] = 1.54 in iterations), and no new workgroup could start in its place.  The launch bounds, the block offset, the grid and
+// the byte count of the launch follow this one number; 2 and 4 were the other two builds of
+// profiles/r08a_k4_one_frame_per_workgroup.txt (compose + K4 0.2170 ms at 4, 0.2079 at 2, 0.2002 at 1; the same bytes out).
+constexpr int PW_WAVES = 1;
 constexpr int PW_MINW = 4;  // waves per SIMD asked of the register allocator (<= 128 VGPRs)
 constexpr double SVO_EPS = 0.0000000001;  // svo/include/svo/global.h:77
 
@@ -545,7 +552,7 @@ namespace svo_track {
 // n_stride <= 256 only (the radix select keeps 4 keys per lane in registers); the caller falls back to the ordered kernel beyond
 int launch_pose_wave(const PoseWaveArgs& a, hipStream_t s) {
   const int grid = (a.B + PW_WAVES - 1) / PW_WAVES;
-  const size_t lds = (size_t)PW_WAVES * pw_cap(a.n_stride) * PW_BYTES_PER_OBS;  // <= 46 080 bytes
+  const size_t lds = (size_t)PW_WAVES * pw_cap(a.n_stride) * PW_BYTES_PER_OBS;  // <= PW_WAVES * 11 520 bytes
   hipLaunchKernelGGL(pose_opt_wave_kernel, dim3(grid), dim3(64 * PW_WAVES), lds, s, a);
   return check_launch();
 }
