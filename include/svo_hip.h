@@ -1025,6 +1025,109 @@ int svo_hip_initialize_seeds(const svo_hip_camera* cam, int n_frames, int n_cell
                              const int32_t* d_frame_index, const double* d_depth_mean, const double* d_depth_min,
                              int batch_id, int seed_stride, const svo_hip_seed_init_out* out, void* stream);
 
+/* ---- K11: the end of a tracked frame (frame_handler_mono.cpp:151-193, 224-229, 304-315) ------------------------- */
+/*
+ * What FrameHandlerMono::processFrame does after the reprojector and the pose optimizer, for B sequences in one launch:
+ * the failure gates, setTrackingQuality, getSceneDepth, needNewKf, setKeyframe(), the occupancy initializeSeeds' detector
+ * needs, getFurthestKeyframe, and the next sparse alignment's xyz_ref / valid.  It reads what svo_hip_select_matches
+ * and svo_hip_pose_optimize write, and writes what svo_hip_sparse_align, svo_hip_fast_detect and
+ * svo_hip_initialize_seeds read.  All of it is f64 with separate roundings; sequential scans of the reference are
+ * stated as arg-max / arg-min rules, so the outputs are the bits of tests/frame_close_checker.py's sequential loops.
+ *
+ * Inputs per sequence b (svo_hip_frame_close_in).  Rows [b * n_stride, b * n_stride + n[b]) are the frame's fts_ in list
+ * order; n = d_n[b] clamped to [0, n_stride].  d_px [..][2], d_f [..][3], d_pos [..][3] f64 (pos is read only where the
+ * row has a point); d_has_point [..] u8 as svo_hip_pose_optimize leaves it (0 = Feature::point == NULL, pruned ones
+ * included); d_T_f_w [12] the refined pose; d_T_last [12] = last_frame_->T_f_w_; d_num_obs = sfba_n_edges_final;
+ * d_num_obs_last = num_obs_last_.  The keyframes in Map::keyframes_ order: n_kf = d_n_kf[b] clamped to [0, kf_stride],
+ * d_kf_T [kf_stride][12], d_kf_overlap [kf_stride] i32 (>= 0: the keyframe is in overlap_kfs_ -- the rank
+ * svo_hip_frame_pose_compose / svo_hip_reproject_map use --, -1: it is not).  The grid is svo_hip_first_map's; cam gives
+ * width and height only.  No output may alias an input.
+ *  1. Gates.  gate = 1 when n < quality_min_fts (:151; the reference's n_matches_ is the number of selected features);
+ *     else 2 when num_obs < min_pose_obs (:170); else 3 when setTrackingQuality(num_obs) gives TRACKING_INSUFFICIENT
+ *     (frame_handler_base.cpp:157-171: num_obs < quality_min_fts, or int(min(num_obs_last, max_fts)) - num_obs >
+ *     quality_max_drop_fts); else 0.  quality = SVO_HIP_TRACKING_INSUFFICIENT at any gate (at gate 2 that is what
+ *     finishFrameProcessingCommon leaves, frame_handler_base.cpp:132-137), SVO_HIP_TRACKING_GOOD otherwise
+ *     (setTrackingQuality never gives TRACKING_BAD).  result = SVO_HIP_RESULT_FAILURE at any gate, else
+ *     SVO_HIP_RESULT_NO_KEYFRAME when needNewKf is false (kf_block >= 0), else SVO_HIP_RESULT_IS_KEYFRAME.
+ *     T_out = T_last at gates 1 and 3 (:154, :183), the refined pose otherwise (gate 2 keeps it, as the reference does);
+ *     a copy of the twelve inputs.  nobs_out = Frame::nObs(), the rows with a point: what finishFrameProcessingCommon
+ *     stores into num_obs_last_.
+ *  2. Scene depth (frame.cpp:167-188) over the rows with a point, in row order: z = (T_out * pos).z with T_out as a unit
+ *     quaternion and a translation (csrc/track_math.h: se3_from_Rt, se3_apply); depth_min = fmin from DBL_MAX;
+ *     depth_mean = the element of rank floor(m / 2) of the m depths (vk::getMedian; ties by row).  No point: both 0.
+ *     Computed for every sequence whatever its result (the reference does not reach the call after a failure).
+ *  3. needNewKf (:304-315), for every keyframe i < n_kf with kf_overlap >= 0: relpos = T_out * kf_pos, kf_pos =
+ *     T_kf.inverse().translation(); it blocks when |x| / depth_mean < kfselect_mindist and |y| / depth_mean <
+ *     kfselect_mindist * 0.8 and |z| / depth_mean < kfselect_mindist * 1.3 (divisions as written: depth_mean == 0
+ *     blocks nothing).  kf_block = the smallest blocking index, or -1.
+ *  4. The next reference of svo_hip_sparse_align (sparse_img_align.cpp:102-108): valid = the row has a point; xyz_ref =
+ *     f * sqrt((dx dx + dy dy) + dz dz), d = pos - T_out.inverse().translation().  Rows without a point and rows
+ *     beyond n: 0.  (d_px goes to svo_hip_sparse_align as it is.)
+ *  5. Keyframe outputs, written for every sequence, meaningful where result is SVO_HIP_RESULT_IS_KEYFRAME.
+ *     key_pts [5]: row indices, Frame::setKeyPoints on a frame that had none -- svo_hip_first_map's rules 2 over the
+ *     rows with a point (ties to the smallest row, -0 and +0 tie, the NaN rule, -1 for an empty set).
+ *     occupancy [cells]: setExistingFeatures over ALL rows < n, with or without a point (feature_detection.cpp:42-49,
+ *     depth_filter.cpp:117), with svo_hip_first_map's guard for pixels that are not finite or outside the grid.
+ *     kf_remove: when max_n_kfs > 2 and n_kf >= max_n_kfs (:224), Map::getFurthestKeyframe(T_out.inverse().translation())
+ *     (map.cpp:149-162): the arg-max over i < n_kf of sqrt((dx dx + dy dy) + dz dz), d = kf_pos - frame_pos, under a
+ *     strict > from 0.0, the first keyframe in list order winning ties; -1 when no distance exceeds 0 (the reference
+ *     would dereference a null pointer there) and in every other case.
+ * Every element of every output is written by the launch.  One workgroup per sequence, integer atomics only: the same
+ * call gives the same bits, and so do identical sequences at different batch positions.
+ * Limits: a null pointer (the row arrays only where n_stride > 0, the keyframe arrays only where kf_stride > 0, the
+ * occupancy only where cells > 0), a negative size, cell_size <= 0 or cells != grid_n_cols * grid_n_rows:
+ * SVO_HIP_EINVAL; n_stride > 1024 or kf_stride > 64: SVO_HIP_ERANGE; B == 0 is a successful no-op that touches nothing.
+ */
+#define SVO_HIP_TRACKING_INSUFFICIENT 0 /* FrameHandlerBase::TrackingQuality, frame_handler_base.h:53-57 */
+#define SVO_HIP_TRACKING_BAD 1
+#define SVO_HIP_TRACKING_GOOD 2
+#define SVO_HIP_RESULT_NO_KEYFRAME 0 /* FrameHandlerBase::UpdateResult, frame_handler_base.h:58-62 */
+#define SVO_HIP_RESULT_IS_KEYFRAME 1
+#define SVO_HIP_RESULT_FAILURE 2
+typedef struct svo_hip_frame_close_params {
+  int32_t quality_min_fts;      /* Config::qualityMinFts(), 50 (config.cpp:53)     */
+  int32_t quality_max_drop_fts; /* Config::qualityMaxFtsDrop(), 40 (config.cpp:54) */
+  int32_t max_fts;              /* Config::maxFts(), 120 (config.cpp:52)           */
+  int32_t max_n_kfs;            /* Config::maxNKfs(), 10 (config.cpp:50)           */
+  double kfselect_mindist;      /* Config::kfSelectMinDist(), 0.12 (config.cpp:46) */
+  int32_t min_pose_obs;         /* 20, the literal at frame_handler_mono.cpp:170   */
+  int32_t reserved;
+} svo_hip_frame_close_params;
+typedef struct svo_hip_frame_close_in {
+  const int32_t* d_n;            /* [B]                  */
+  const double* d_px;            /* [B][n_stride][2]     */
+  const double* d_f;             /* [B][n_stride][3]     */
+  const double* d_pos;           /* [B][n_stride][3]     */
+  const uint8_t* d_has_point;    /* [B][n_stride]        */
+  const double* d_T_f_w;         /* [B][12]              */
+  const double* d_T_last;        /* [B][12]              */
+  const int32_t* d_num_obs;      /* [B]                  */
+  const int32_t* d_num_obs_last; /* [B]                  */
+  const int32_t* d_n_kf;         /* [B]                  */
+  const double* d_kf_T;          /* [B][kf_stride][12]   */
+  const int32_t* d_kf_overlap;   /* [B][kf_stride]       */
+} svo_hip_frame_close_in;
+typedef struct svo_hip_frame_close_out {
+  int32_t* d_gate;      /* [B] 0 .. 3                                        */
+  int32_t* d_quality;   /* [B] SVO_HIP_TRACKING_*                            */
+  int32_t* d_result;    /* [B] SVO_HIP_RESULT_*                              */
+  double* d_T_out;      /* [B][12]                                           */
+  int32_t* d_nobs_out;  /* [B]                                               */
+  double* d_depth_mean; /* [B]                                               */
+  double* d_depth_min;  /* [B]                                               */
+  int32_t* d_kf_block;  /* [B] keyframe index, -1 = needNewKf is true        */
+  uint8_t* d_valid;     /* [B][n_stride], svo_hip_sparse_align's d_valid     */
+  double* d_xyz_ref;    /* [B][n_stride][3], svo_hip_sparse_align's          */
+  int32_t* d_key_pts;   /* [B][5] rows, -1 = NULL                            */
+  uint8_t* d_occupancy; /* [B][cells], svo_hip_fast_detect's d_occupancy     */
+  int32_t* d_kf_remove; /* [B] keyframe index, -1 = none                     */
+} svo_hip_frame_close_out;
+/* host-only: (50, 40, 120, 10, 0.12, 20) */
+int svo_hip_frame_close_params_default(svo_hip_frame_close_params* out);
+int svo_hip_frame_close(const svo_hip_camera* cam, int B, int n_stride, int kf_stride,
+                        const svo_hip_frame_close_in* in, int cell_size, int grid_n_cols, int grid_n_rows, int cells,
+                        const svo_hip_frame_close_params* params, const svo_hip_frame_close_out* out, void* stream);
+
 /* static DepthFilter::computeTau(T_ref_cur, f, z, px_error_angle) (depth_filter.cpp:334-350) for S
  * independent measurements: d_t_ref_cur [S][3] = T_ref_cur.translation(), d_f [S][3], d_z [S].
  * Arithmetic (since round 5, here and inside svo_hip_update_seeds*): the ALGEBRAIC form -- alpha and beta enter only

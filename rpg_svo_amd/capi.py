@@ -144,7 +144,31 @@ class SeedInitOut(C.Structure):
     _fields_ = [("d_" + n, C.c_void_p) for n in SEED_INIT_OUTPUTS]
 
 
+class FrameCloseParams(C.Structure):
+    """svo_hip_frame_close_params: the Config values the end of a tracked frame reads."""
+    _fields_ = [("quality_min_fts", C.c_int32), ("quality_max_drop_fts", C.c_int32), ("max_fts", C.c_int32), ("max_n_kfs", C.c_int32),
+                ("kfselect_mindist", C.c_double), ("min_pose_obs", C.c_int32), ("reserved", C.c_int32)]
+
+
+FRAME_CLOSE_INPUTS = ("n", "px", "f", "pos", "has_point", "T_f_w", "T_last", "num_obs", "num_obs_last", "n_kf", "kf_T", "kf_overlap")
+FRAME_CLOSE_OUTPUTS = ("gate", "quality", "result", "T_out", "nobs_out", "depth_mean", "depth_min", "kf_block", "valid", "xyz_ref",
+                       "key_pts", "occupancy", "kf_remove")
+
+
+class FrameCloseIn(C.Structure):
+    """svo_hip_frame_close_in: inputs of svo_hip_frame_close (device pointers)."""
+    _fields_ = [("d_" + n, C.c_void_p) for n in FRAME_CLOSE_INPUTS]
+
+
+class FrameCloseOut(C.Structure):
+    """svo_hip_frame_close_out: outputs of svo_hip_frame_close (device pointers)."""
+    _fields_ = [("d_" + n, C.c_void_p) for n in FRAME_CLOSE_OUTPUTS]
+
+
 INIT_FAILURE, INIT_NO_KEYFRAME, INIT_SUCCESS = 0, 1, 2
+TRACKING_INSUFFICIENT, TRACKING_BAD, TRACKING_GOOD = 0, 1, 2
+RESULT_NO_KEYFRAME, RESULT_IS_KEYFRAME, RESULT_FAILURE = 0, 1, 2
+FRAME_CLOSE_MAX_ROWS, FRAME_CLOSE_MAX_KFS = 1024, 64
 FIRST_MAP_MAX_PTS = 1024
 HOMOGRAPHY_OK, HOMOGRAPHY_NO_MODEL, HOMOGRAPHY_DEGENERATE = 0, 1, 2
 HOMOGRAPHY_MAX_PTS, HOMOGRAPHY_MAX_HYPOTHESES = 1024, 4096
@@ -255,6 +279,9 @@ PROTOTYPES = {
                                C.POINTER(FirstMapOut), _vp]),
     "svo_hip_initialize_seeds": (_i, [C.POINTER(Camera), _i, _i, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _i, _i,
                                       C.POINTER(SeedInitOut), _vp]),
+    "svo_hip_frame_close_params_default": (_i, [C.POINTER(FrameCloseParams)]),
+    "svo_hip_frame_close": (_i, [C.POINTER(Camera), _i, _i, _i, C.POINTER(FrameCloseIn), _i, _i, _i, _i, C.POINTER(FrameCloseParams),
+                                 C.POINTER(FrameCloseOut), _vp]),
     "svo_hip_compute_tau_batch": (_i, [_i, _vp, _vp, _vp, C.c_double, _vp, _vp]),
 }
 

@@ -23,6 +23,7 @@
 #pragma clang fp contract(off)
 #include "block_select.h"
 #include "capi_common.h"
+#include "frame_keys.h"
 #include "track_math.h"
 
 using namespace svo_capi;
@@ -33,7 +34,6 @@ namespace {
 constexpr int FM_MAX_PTS = 1024;
 constexpr int FM_THREADS = 256;
 constexpr int FM_KEYS = 10;      // key point k of view v is key 5 v + k
-constexpr int FM_NONE = 0x7fffffff;
 
 struct FirstMapArgs {
   int n_pts;
@@ -50,45 +50,6 @@ struct FirstMapArgs {
   svo_hip_first_map_out o;
 };
 
-// v -> an unsigned key with the order of the doubles (v is not NaN; -0 and +0 get different keys)
-__device__ __forceinline__ unsigned long long ordered_key(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ordered_value(unsigned long long k) {
-  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
-
-// What checkKeyPoints compares for the feature at (px0, px1): key point k is the member with the LARGEST key[k].
-// k = 0 is the feature closest to the centre in the maximum norm, so its key is the complement of the distance's.
-// Keys are > 0; a NaN value has no key (nan[k]).  A zero product is +0 whatever its sign: -0 > +0 is false.
-struct KeyVals {
-  bool member[5], nan[5];
-  unsigned long long key[5];
-};
-__device__ __forceinline__ KeyVals key_values(double px0, double px1, int cu, int cv) {
-  KeyVals r;
-  const double dx = px0 - (double)cu, dy = px1 - (double)cv;
-  const double ax = fabs(dx), ay = fabs(dy);
-  const double dist = (ax < ay) ? ay : ax;  // std::max(ax, ay)
-  double prod = dx * dy;
-  prod = (prod == 0.0) ? 0.0 : prod;
-  r.member[0] = true;
-  r.member[1] = px0 >= (double)cu && px1 >= (double)cv;
-  r.member[2] = px0 >= (double)cu && px1 < (double)cv;
-  r.member[3] = px0 < (double)cv && px1 < (double)cv;   // (frame.cpp:110 tests px[0] against cv)
-  r.member[4] = px0 < (double)cv && px1 >= (double)cv;  // (frame.cpp:118 likewise)
-  r.nan[0] = dist != dist;
-  r.key[0] = ~ordered_key(dist);
-#pragma unroll
-  for (int k = 1; k < 5; ++k) {
-    r.nan[k] = prod != prod;
-    r.key[k] = ordered_key(prod);
-  }
-  return r;
-}
-
 __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArgs a) {
   __shared__ double s_z[FM_MAX_PTS];               // depth in the current frame, by rank
   __shared__ int s_idx[FM_MAX_PTS];                // rank -> corner index
@@ -104,14 +65,9 @@ __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArg
   const svo_hip_first_map_out& o = a.o;
   const bool success = a.result[seq] == SVO_HIP_INIT_SUCCESS;  // (workgroup-uniform)
 
-  if (t < FM_KEYS) {
-    s_key[t] = 0ull;
-    s_first[t] = FM_NONE;
-    s_first_nan[t] = 0;
-    s_rank[t] = FM_NONE;
-  }
+  if (t < FM_KEYS) key_points_init(s_key, s_first, s_first_nan, s_rank, t);
   if (t == 0) {
-    s_key[FM_KEYS] = ~ordered_key(1.7976931348623157e308);  // depth_min starts at numeric_limits<double>::max()
+    s_key[FM_KEYS] = depth_min_start();
     s_med = 0.0;
   }
   for (int c = t; c < a.cells; c += FM_THREADS) o.d_occupancy[(size_t)seq * a.cells + c] = 0;
@@ -177,20 +133,10 @@ __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArg
       px_out[0][e] = px[0][e];
       px_out[1][e] = px[1][e];
     }
-    // setExistingFeatures of the current frame: a cell index is used only after it is known to lie inside the grid
-    const double qc = px[1][0] / (double)a.cell_size, qr = px[1][1] / (double)a.cell_size;
-    if (qc > -1.0 && qc < (double)a.grid_n_cols && qr > -1.0 && qr < (double)a.grid_n_rows) {  // (false for NaN)
-      const int col = (int)qc, row = (int)qr;
-      if (col >= 0 && col < a.grid_n_cols && row >= 0 && row < a.grid_n_rows)
-        o.d_occupancy[(size_t)seq * a.cells + (size_t)row * a.grid_n_cols + col] = 1;
-    }
+    // setExistingFeatures of the current frame
+    occupancy_mark(o.d_occupancy + (size_t)seq * a.cells, px[1][0], px[1][1], a.cell_size, a.grid_n_cols, a.grid_n_rows);
 #pragma unroll
-    for (int v = 0; v < 2; ++v) {
-      const KeyVals kv = key_values(px[v][0], px[v][1], cu, cv);
-#pragma unroll
-      for (int k = 0; k < 5; ++k)
-        if (kv.member[k]) atomicMin(&s_first[5 * v + k], j);
-    }
+    for (int v = 0; v < 2; ++v) key_points_first(key_values(px[v][0], px[v][1], cu, cv), j, s_first + 5 * v);
   }
   __syncthreads();
 
@@ -200,16 +146,9 @@ __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArg
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
       const float* p = (v == 0 ? a.px_ref : a.px_cur) + 2 * gi;
-      const KeyVals kv = key_values((double)p[0], (double)p[1], cu, cv);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        if (!kv.member[k]) continue;
-        if (!kv.nan[k]) atomicMax(&s_key[5 * v + k], kv.key[k]);
-        else if (s_first[5 * v + k] == j) s_first_nan[5 * v + k] = 1;
-      }
+      key_points_best(key_values((double)p[0], (double)p[1], cu, cv), j, s_key + 5 * v, s_first + 5 * v, s_first_nan + 5 * v);
     }
-    const double z = s_z[j];
-    if (z == z) atomicMax(&s_key[FM_KEYS], ~ordered_key(z));  // fmin skips a NaN
+    depth_min_add(&s_key[FM_KEYS], s_z[j]);
   }
   __syncthreads();
 
@@ -219,24 +158,18 @@ __global__ void __launch_bounds__(FM_THREADS) first_map_kernel(const FirstMapArg
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
       const float* p = (v == 0 ? a.px_ref : a.px_cur) + 2 * gi;
-      const KeyVals kv = key_values((double)p[0], (double)p[1], cu, cv);
-#pragma unroll
-      for (int k = 0; k < 5; ++k)
-        if (kv.member[k] && !kv.nan[k] && kv.key[k] == s_key[5 * v + k]) atomicMin(&s_rank[5 * v + k], j);
+      key_points_rank(key_values((double)p[0], (double)p[1], cu, cv), j, s_key + 5 * v, s_rank + 5 * v);
     }
   }
   // vk::getMedian: rank m / 2 of the m depths; a NaN is never smaller or equal, so it has no rank and adds to none
   block_rank_select<FM_THREADS>(s_z, m, m / 2, t, [&](int j) { return s_z[j] == s_z[j]; }, &s_med);
   __syncthreads();
 
-  if (t < FM_KEYS) {
-    const int first = s_first[t];
-    o.d_key_pts[FM_KEYS * (size_t)seq + t] = first == FM_NONE ? -1 : (s_first_nan[t] ? first : s_rank[t]);
-  }
+  if (t < FM_KEYS) o.d_key_pts[FM_KEYS * (size_t)seq + t] = key_point_result(s_first, s_first_nan, s_rank, t);
   if (t == 0) {
     o.d_n_points[seq] = m;
     o.d_depth_mean[seq] = m > 0 ? s_med : 0.0;
-    o.d_depth_min[seq] = m > 0 ? ordered_value(~s_key[FM_KEYS]) : 0.0;
+    o.d_depth_min[seq] = m > 0 ? depth_min_value(&s_key[FM_KEYS]) : 0.0;
   }
 }
 

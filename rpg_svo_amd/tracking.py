@@ -274,6 +274,179 @@ def optimize_gauss_newton(cam, n, f, level, pos, has_point, T_f_w, reproj_thresh
     return res
 
 
+# ---- the end of FrameHandlerMono::processFrame ------------------------------------------------
+@dataclass
+class FrameClose:
+    """The outputs of svo_hip_frame_close for B sequences (include/svo_hip.h states every one)."""
+    gate: torch.Tensor        # [B] i32   0, or the failure gate that stopped the frame (1 .. 3)
+    quality: torch.Tensor     # [B] i32   capi.TRACKING_*
+    result: torch.Tensor      # [B] i32   capi.RESULT_*
+    T_out: torch.Tensor       # [B,12]    new_frame_->T_f_w_ as processFrame leaves it
+    nobs_out: torch.Tensor    # [B] i32   Frame::nObs(): the next frame's num_obs_last
+    depth_mean: torch.Tensor  # [B] f64
+    depth_min: torch.Tensor   # [B] f64
+    kf_block: torch.Tensor    # [B] i32   the keyframe that made needNewKf false, -1: none
+    valid: torch.Tensor       # [B,ns] u8 K1's `valid` with this frame as the reference
+    xyz_ref: torch.Tensor     # [B,ns,3]  K1's `xyz_ref` likewise
+    key_pts: torch.Tensor     # [B,5] i32 rows, -1 = NULL
+    occupancy: torch.Tensor   # [B,cells] u8, FastDetector.detect's occupancy
+    kf_remove: torch.Tensor   # [B] i32   the keyframe getFurthestKeyframe picks, -1: none is removed
+
+
+_FRAME_CLOSE_DTYPES = dict(gate=torch.int32, quality=torch.int32, result=torch.int32, T_out=torch.float64, nobs_out=torch.int32,
+                           depth_mean=torch.float64, depth_min=torch.float64, kf_block=torch.int32, valid=torch.uint8,
+                           xyz_ref=torch.float64, key_pts=torch.int32, occupancy=torch.uint8, kf_remove=torch.int32)
+
+
+def frame_close_outputs(B: int, n_stride: int, cells: int, device) -> FrameClose:
+    """The tensors of svo_hip_frame_close_out.  Allocate once and hand them to every call that a HIP graph captures."""
+    shape = dict(T_out=(B, 12), valid=(B, n_stride), xyz_ref=(B, n_stride, 3), key_pts=(B, 5), occupancy=(B, cells))
+    return FrameClose(**{k: torch.zeros(shape.get(k, (B,)), dtype=dt, device=device) for k, dt in _FRAME_CLOSE_DTYPES.items()})
+
+
+def frame_close_params(**fields) -> capi.FrameCloseParams:
+    """svo_hip_frame_close_params: the reference's Config values, with the given fields replaced"""
+    p = capi.FrameCloseParams()
+    capi.check(capi.load().svo_hip_frame_close_params_default(C.byref(p)), "svo_hip_frame_close_params_default")
+    for k, v in fields.items():
+        assert k in dict(capi.FrameCloseParams._fields_) and k != "reserved", k
+        setattr(p, k, v)
+    return p
+
+
+def close_frame(cam, n, px, f, pos, has_point, T_f_w, T_last, num_obs, num_obs_last, n_kf, kf_T, kf_overlap, cell_size: int,
+                grid_n_cols: int, grid_n_rows: int, params: capi.FrameCloseParams | None = None,
+                out: FrameClose | None = None) -> FrameClose:
+    """The end of FrameHandlerMono::processFrame for B frames (svo_hip_frame_close): failure gates, tracking quality, scene
+    depth, needNewKf, and for a new keyframe its key points, the detector's occupancy and the keyframe to drop; K1's
+    xyz_ref / valid for the next frame.  n [B] i32, px [B,ns,2] / f [B,ns,3] / pos [B,ns,3] f64 and has_point [B,ns] u8 are
+    the frame's features as select_matches and optimize_gauss_newton leave them; T_f_w / T_last [B,12]; num_obs /
+    num_obs_last [B] i32; the map's keyframes n_kf [B] i32, kf_T [B,nk,12], kf_overlap [B,nk] i32 (-1: not in
+    overlap_kfs_).  params: frame_close_params(...).  out: a FrameClose to reuse (every element is overwritten).
+    Enqueued on the current stream, not synchronised."""
+    B, ns = has_point.shape
+    nk = kf_overlap.shape[1]
+    i32, f64 = torch.int32, torch.float64
+    for t, dt, shape in ((n, i32, (B,)), (px, f64, (B, ns, 2)), (f, f64, (B, ns, 3)), (pos, f64, (B, ns, 3)), (has_point, torch.uint8, (B, ns)),
+                         (T_f_w, f64, (B, 12)), (T_last, f64, (B, 12)), (num_obs, i32, (B,)), (num_obs_last, i32, (B,)), (n_kf, i32, (B,)),
+                         (kf_T, f64, (B, nk, 12)), (kf_overlap, i32, (B, nk))):
+        assert _chk(t, dt) is t and tuple(t.shape) == shape, (tuple(t.shape), shape)
+    dev = has_point.device
+    cells = grid_n_cols * grid_n_rows
+    out = frame_close_outputs(B, ns, cells, dev) if out is None else out
+    for k, dt in _FRAME_CLOSE_DTYPES.items():
+        t = getattr(out, k)
+        assert t.dtype == dt and t.is_contiguous() and t.device == dev
+    assert tuple(out.occupancy.shape) == (B, cells) and tuple(out.valid.shape) == (B, ns) and tuple(out.gate.shape) == (B,)
+    p = params if params is not None else frame_close_params()
+    i = capi.FrameCloseIn(*[_ptr(t) for t in (n, px, f, pos, has_point, T_f_w, T_last, num_obs, num_obs_last, n_kf, kf_T, kf_overlap)])
+    o = capi.FrameCloseOut(*[_ptr(getattr(out, k)) for k in capi.FRAME_CLOSE_OUTPUTS])
+    c = capi.camera(cam)
+    capi.check(capi.load().svo_hip_frame_close(C.byref(c), B, ns, nk, C.byref(i), int(cell_size), int(grid_n_cols), int(grid_n_rows), cells,
+                                               C.byref(p), C.byref(o), _stream_ptr(dev)), "svo_hip_frame_close")
+    return out
+
+
+@dataclass
+class TrackedFrame:
+    """What track_from_first_map leaves on the device for n sequences (m = the first map's stride, cap = min(m, max_fts + 1))."""
+    align: object               # SparseAlignResult of K1 (T_cur_from_ref, n_tracked, ...)
+    frames: FrameTable          # rows [0, n): first keyframes, [n, 2n): second keyframes, [2n, 3n): the tracked frames
+    order: torch.Tensor         # [n,m] i64  trial t of a sequence is map rank order[t] (the reprojector's visiting order)
+    n_trials: torch.Tensor      # [n] i32    Reprojector::n_trials_: the points inside the frame
+    match: MatchResult          # [n*m] findMatchDirect per trial, trials beyond n_trials skipped (ok == 0)
+    n_matches: torch.Tensor     # [n] i32    Reprojector::n_matches_ = the frame's features
+    sel: torch.Tensor           # [n,cap] i32 the trial behind each feature, -1 beyond n_matches
+    px: torch.Tensor            # [n,cap,2]  the new frame's Feature::px ..
+    f: torch.Tensor             # [n,cap,3]  .. f
+    level: torch.Tensor         # [n,cap] i32
+    pos: torch.Tensor           # [n,cap,3]  the features' points
+    pose: PoseOptResult         # optimizeGaussNewton: T_f_w, stats, has_point after pruning
+    num_obs: torch.Tensor       # [n] i32    sfba_n_edges_final
+    close: FrameClose
+
+
+def track_from_first_map(store: PyramidStore, cam, fm, kf_slots, kf_T, next_slots, grid, detector_grid, num_obs_last=None,
+                         params: capi.FrameCloseParams | None = None, max_fts: int = 120, sia=None, matcher: Matcher | None = None,
+                         close_out: FrameClose | None = None) -> TrackedFrame:
+    """The first FrameHandlerMono::processFrame after the bootstrap (frame_handler_mono.cpp:129-193), for the n sequences of a
+    FirstMap `fm` (initialization.KltHomographyInit.first_map), enqueued on the current stream without a host read:
+      1. SparseImgAlign.run, second keyframe -> next image, on fm.px[:, 1] / fm.xyz_ref / fm.n_points with an identity prior;
+      2. compose_poses: the new frame's T_f_w into the frame table;
+      3. reproject_points of the map points (ranks beyond n_points are no trials);
+      4. Matcher.find_match_direct with two observation records per point, view 0 then view 1 (Point::obs_ after the two
+         addFrameRef calls of initialization.cpp:78-97, which push to the front);
+      5. select_matches per sequence; 6. optimize_gauss_newton; 7. close_frame.
+    kf_slots = (slots of the first keyframes, of the second) [n] i32 each, kf_T = (T_ref_w, T_cur_w) [n,12] each, next_slots
+    [n] i32.  grid: map_mirror.Grid, the reprojector's grid with its cell order; detector_grid = (cell_size, n_cols, n_rows) of
+    the feature detector, for the occupancy.  num_obs_last [n] i32 defaults to fm.n_points (Frame::nObs() of the second
+    keyframe, what processSecondFrame leaves in num_obs_last_).
+    Every map point is TYPE_UNKNOWN and a cell's list sort is stable, so the visiting order is a stable sort of the in-frame
+    points by the rank of their cell; that sort, the gathers and the record offsets are torch operations (plumbing).
+    The map is the two keyframes of the first map: kf_overlap is 0 for both -- overlap_kfs_ holds every close keyframe
+    (reprojector.cpp:75-80); Map::getCloseKeyframes' visibility test of the key points is not mirrored."""
+    from .sparse_img_align import SparseImgAlign
+    dev = store.device
+    n, m = fm.pos.shape[0], fm.pos.shape[1]
+    M = n * m
+    i32, f64 = torch.int32, torch.float64
+    T_ref_w, T_cur_w = kf_T
+    sia = sia if sia is not None else SparseImgAlign(4, 2)
+    matcher = matcher if matcher is not None else Matcher()
+    # 1. K1
+    prior = torch.tensor([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=f64, device=dev).repeat(n, 1)
+    align = sia.run(store, cam, _chk(kf_slots[1], i32), _chk(next_slots, i32), fm.n_points, fm.px[:, 1].contiguous(), fm.xyz_ref, prior)
+    # 2. the frame table and the new frame's pose
+    frame_T = torch.cat([T_ref_w, T_cur_w, T_cur_w]).contiguous()
+    frames = FrameTable(torch.cat([kf_slots[0], kf_slots[1], next_slots]).contiguous(), frame_T)
+    cur_rows = torch.arange(2 * n, 3 * n, dtype=i32, device=dev)
+    compose_poses(align.T_cur_from_ref, _chk(T_cur_w, f64), out=frame_T, out_index=cur_rows)
+    # 3. Reprojector::reprojectPoint
+    cur_frame = cur_rows.repeat_interleave(m).contiguous()
+    cell, px_proj = reproject_points(cam, frames, cur_frame, fm.pos.reshape(M, 3), grid.cell_size, grid.n_cols)
+    rank = torch.arange(m, device=dev)[None, :]
+    in_frame = (cell.view(n, m) >= 0) & (rank < fm.n_points[:, None])
+    # the visiting order: cells in grid_.cell_order, the points of a cell in map order
+    key = torch.where(in_frame, grid.cell_rank.long()[cell.view(n, m).clamp(min=0).long()], grid.n_cols * grid.n_rows)
+    order = torch.sort(key, dim=1, stable=True).indices
+    take = lambda t: torch.gather(t, 1, order.view(n, m, *([1] * (t.dim() - 2))).expand(n, m, *t.shape[2:])).contiguous()
+    t_in = take(in_frame)
+    t_cell = torch.where(t_in, take(cell.view(n, m)), -1).to(i32).contiguous()
+    t_pos, t_px = take(fm.pos), take(px_proj.view(n, m, 2))
+    n_trials = t_in.sum(dim=1, dtype=i32)
+    # 4. two observation records per trial, compacted: the records of a skipped trial go to two spare slots at the end
+    ptr = torch.zeros(M + 1, dtype=i32, device=dev)
+    ptr[1:] = torch.cumsum(2 * t_in.reshape(M).to(i32), 0)
+    first = torch.where(t_in.reshape(M), ptr[:-1].long(), 2 * M)
+    second = torch.where(t_in.reshape(M), ptr[:-1].long() + 1, 2 * M + 1)
+    obs = FeatureSet(frame=torch.zeros(2 * M + 2, dtype=i32, device=dev), level=torch.zeros(2 * M + 2, dtype=i32, device=dev),
+                     px=torch.zeros(2 * M + 2, 2, dtype=f64, device=dev), f=torch.zeros(2 * M + 2, 3, dtype=f64, device=dev))
+    seq = torch.arange(n, dtype=i32, device=dev).repeat_interleave(m)
+    for view, at in ((0, first), (1, second)):
+        obs.frame.index_copy_(0, at, seq + view * n)
+        obs.px.index_copy_(0, at, take(fm.px[:, view]).reshape(M, 2))
+        obs.f.index_copy_(0, at, take(fm.f[:, view]).reshape(M, 3))
+    match = matcher.find_match_direct(store, cam, frames, cur_frame, t_pos.reshape(M, 3), ptr, obs, t_px.reshape(M, 2))
+    # 5. the cell loop of reprojectMap, sequence by sequence
+    picked = [select_matches(cam, t_cell[b], match.ok.view(n, m)[b], match.px_cur.view(n, m, 2)[b], match.search_level.view(n, m)[b],
+                             t_pos[b], max_fts) for b in range(n)]
+    n_matches = torch.cat([p[0] for p in picked])
+    sel, f, level, pos, has_point = (torch.stack([p[k] for p in picked]).contiguous() for k in range(1, 6))
+    chosen = sel >= 0
+    px = torch.gather(match.px_cur.view(n, m, 2), 1, sel.clamp(min=0).long()[..., None].expand(-1, -1, 2))
+    px = torch.where(chosen[..., None], px, 0.0).contiguous()
+    # 6. pose_optimizer::optimizeGaussNewton from the aligned pose
+    pose = optimize_gauss_newton(cam, n_matches, f, level, pos, has_point, frame_T[2 * n:])
+    num_obs = pose.stats[:, 3].to(i32)
+    # 7. the end of the frame
+    last = fm.n_points if num_obs_last is None else num_obs_last
+    two = torch.full((n,), 2, dtype=i32, device=dev)
+    close = close_frame(cam, n_matches, px, f, pos, pose.has_point, pose.T_f_w, T_cur_w, num_obs, _chk(last, i32), two,
+                        torch.stack([T_ref_w, T_cur_w], dim=1).contiguous(), torch.zeros(n, 2, dtype=i32, device=dev), *detector_grid,
+                        params=params, out=close_out)
+    return TrackedFrame(align, frames, order, n_trials, match, n_matches, sel, px, f, level, pos, pose, num_obs, close)
+
+
 # ---- Point::optimize ----------------------------------------------------------------------
 def point_optimize(frames: FrameTable, obs_ptr, obs_frame, obs_f, pos, n_iter: int = 5):
     """Point::optimize(n_iter) for P points; returns the optimised positions [P,3]."""

@@ -16,7 +16,11 @@ CPU path, and nothing is measured without one (the JSON then says "not measured"
 csrc/first_map.hip; the detector between them is K7's and is not timed here) on 1 x 416 and 4096 x 416 corners (the 26 x 16
 grid of a 752 x 480 image, about 260 map points and 170 new corners per sequence) and writes profiles/first_map_bench.json:
 the same device events, the two kernels' own times from the same kind of rocprofv3 run, and the bytes the step moves, from
-the shapes, against the HBM rate."""
+the shapes, against the HBM rate.
+
+--step frame_close times the end of a tracked frame (svo_hip_frame_close, csrc/frame_close.hip) on 1 and 4096 sequences x 121
+rows x 10 keyframes (max_fts + 1 features, a full keyframe list) and writes profiles/frame_close_bench.json in the same
+form: device events, the kernel's own time from a rocprofv3 run of its own, the compiler's figures and the bytes per sequence."""
 from __future__ import annotations
 
 import argparse
@@ -243,6 +247,112 @@ def main_first_map(args):
     print(json.dumps(res))
 
 
+# ---- the end of a tracked frame (K11) -----------------------------------------------------------------------------------
+ROWS, KEYFRAMES = 121, 10
+FRAME_CLOSE_KERNEL = "frame_close_kernel"
+
+
+def frame_close_bytes(rows, kfs, cells, share=0.7):
+    """bytes one sequence moves: every output element is written once; a row's pixel is read for the occupancy and, where it
+    has a point (share of the rows), twice more for the key points; position and bearing only where the row has a point"""
+    read = 4 * 4 + 2 * 96 + rows * (1 + 16) + share * rows * (2 * 16 + 24 + 24) + kfs * (96 + 4)
+    written = 6 * 4 + 96 + 2 * 8 + rows * (1 + 24) + 5 * 4 + cells
+    return read + written
+
+
+def compiler_resources_frame_close():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    with tempfile.TemporaryDirectory() as tmp:
+        from rpg_svo_amd.build import FLAGS
+        r = subprocess.run([hipcc, *FLAGS, "-c", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rpg_svo_amd", "csrc"),
+                            os.path.join(ROOT, "rpg_svo_amd", "csrc", "frame_close.hip"), "-o", os.path.join(tmp, "fc.o"),
+                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    for blk in r.stderr.split("Function Name: ")[1:]:
+        if FRAME_CLOSE_KERNEL in blk.split()[0]:
+            g = lambda key: int(re.search(key + r": (\d+)", blk).group(1))
+            return {"vgprs": g("VGPRs"), "agprs": g("AGPRs"), "sgprs": g("TotalSGPRs"), "scratch_bytes_per_lane": g(r"ScratchSize \[bytes/lane\]"),
+                    "occupancy_waves_per_simd": g(r"Occupancy \[waves/SIMD\]"), "lds_bytes_per_block": g(r"LDS Size \[bytes/block\]")}
+    return "not measured"
+
+
+def time_frame_close(dev, n_seq, steps, warmup):
+    import numpy as np
+    import torch
+    import first_map_cases
+    import frame_close_cases as cases
+    from rpg_svo_amd import tracking as tr
+    cam = first_map_cases.camera(752, 480)
+    distinct = min(DISTINCT, n_seq)
+    b = cases._batch("bench", [cases.make_seq(cam, 8000 + k, ROWS, ROWS, n_kf=KEYFRAMES, kf_stride=KEYFRAMES, num_obs=85, num_obs_last=100)
+                               for k in range(distinct)], GRID[0])
+    assert b.grid == GRID
+    reps = -(-n_seq // distinct)
+    inp = [torch.from_numpy(np.tile(v, (reps,) + (1,) * (v.ndim - 1))[:n_seq].copy()).to(dev) for v in cases.inputs(b).values()]
+    out, times = None, []
+    for i in range(warmup + steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = tr.close_frame(cam, *inp, *GRID, out=out)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            times.append(e0.elapsed_time(e1))
+    times.sort()
+    med = times[len(times) // 2]
+    return {"sequences": n_seq, "rows": ROWS, "keyframes": KEYFRAMES, "cells": GRID[1] * GRID[2], "steps": steps, "call_ms_median": med,
+            "call_ms_min": times[0], "call_ms_max": times[-1], "sequences_per_s": n_seq / (med * 1e-3),
+            "mean_points": float(out.nobs_out.float().mean().item()), "keyframe_fraction": float((out.result == 1).float().mean().item()),
+            "bytes_per_sequence": frame_close_bytes(ROWS, KEYFRAMES, GRID[1] * GRID[2])}
+
+
+def traced_frame_close_ms(args):
+    """Kernel time of the replay shape from rocprofv3's kernel trace, in a run of its own."""
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    out = tempfile.mkdtemp(prefix="frame_close_trace_", dir=os.path.join(ROOT, "build"))
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "trace", "--", sys.executable,
+           os.path.abspath(__file__), "--step", "frame_close", "--traced-child", "--pairs", str(args.pairs)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    files = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
+    if r.returncode != 0 or not files:
+        return {"error": f"rocprofv3 exit {r.returncode}: {r.stderr[-400:]}"}
+    for row in csv.DictReader(open(files[0])):
+        if FRAME_CLOSE_KERNEL in row.get("Name", ""):
+            return {"calls": int(row["Calls"]), "average_ms": float(row["AverageNs"]) * 1e-6, "min_ms": float(row["MinNs"]) * 1e-6,
+                    "max_ms": float(row["MaxNs"]) * 1e-6}
+    return {"error": "the kernel is not in the trace"}
+
+
+def main_frame_close(args):
+    import torch
+    out = args.out or os.path.join(ROOT, "profiles", "frame_close_bench.json")
+    nbytes = frame_close_bytes(ROWS, KEYFRAMES, GRID[1] * GRID[2])
+    if not torch.cuda.is_available():
+        res = {"device": "not measured", "single_sequence": "not measured", "replay_batch": "not measured", "rocprofv3": "not measured",
+               "compiler": "not measured" if args.no_compiler else compiler_resources_frame_close(), "bytes_per_sequence": nbytes,
+               "note": "no MI355X was available: nothing here is measured without one"}
+    else:
+        dev = torch.device("cuda:0")
+        if args.traced_child:
+            time_frame_close(dev, args.pairs, 3, 1)
+            return
+        res = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("SVO_HIP_LIB", "in-tree")}
+        res["single_sequence"] = time_frame_close(dev, 1, max(args.steps, 10), 5)
+        res["single_sequence"]["note"] = "one workgroup: launch-bound"
+        res["replay_batch"] = time_frame_close(dev, args.pairs, args.steps, args.warmup)
+        res["compiler"] = "not measured" if args.no_compiler else compiler_resources_frame_close()
+        res["rocprofv3"] = "not measured" if args.no_trace else traced_frame_close_ms(args)
+        kern = res["rocprofv3"].get("average_ms") if isinstance(res["rocprofv3"], dict) else None
+        t_ms = kern if kern else res["replay_batch"]["call_ms_median"]
+        res["hbm_bound"] = {"time_basis": "rocprofv3 kernel time" if kern else "device events", "time_ms": t_ms, "bytes": nbytes * args.pairs,
+                            "peak_bytes_per_s": PEAK_HBM_BYTES, "least_ms_by_bytes": nbytes * args.pairs / PEAK_HBM_BYTES * 1e3,
+                            "achieved_bytes_per_s": nbytes * args.pairs / (t_ms * 1e-3), "share_of_bound": nbytes * args.pairs / PEAK_HBM_BYTES * 1e3 / t_ms}
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--pairs", type=int, default=4096)
@@ -251,11 +361,13 @@ def main():
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--no-compiler", action="store_true", help="skip the compile that reports registers, scratch and occupancy")
     ap.add_argument("--traced-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--step", choices=("homography", "first_map"), default="homography", help="which step of the bootstrap to time")
-    ap.add_argument("--out", default=None, help="default: profiles/homography_bench.json or profiles/first_map_bench.json")
+    ap.add_argument("--step", choices=("homography", "first_map", "frame_close"), default="homography", help="which step of the bootstrap to time")
+    ap.add_argument("--out", default=None, help="default: profiles/<step>_bench.json")
     args = ap.parse_args()
     if args.step == "first_map":
         return main_first_map(args)
+    if args.step == "frame_close":
+        return main_frame_close(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "homography_bench.json")
     import torch
     if not torch.cuda.is_available():
