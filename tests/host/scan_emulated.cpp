@@ -9,10 +9,12 @@
 extern "C" {
 
 // Warps and scans seeds [0, S) (`form` is unused: there is one form of the scan).  One level-`n_levels` store of one slot;
-// workspace arrays as SeedWs names them (only what the scan kernel reads and writes).
+// workspace arrays as SeedWs names them (only what the scan kernel reads and writes).  The camera whole: cam_k = fx, fy, cx,
+// cy, its size, cam_model (SVO_HIP_CAM_*) and the five distortion parameters; a distorted camera runs the instantiation
+// epi_scan_kernel<false> runs, epi_scan_seed<false>.
 int scan_emulated(int form, int S, const uint8_t* store, long long slot_bytes, int n_levels, const long long* level_offset,
                   const int* level_w, const int* level_h, const int* level_pitch, const double cam_k[4], int width, int height,
-                  int subpix_refinement, const int32_t* search_level, const int32_t* cur_slot, const int32_t* n_steps, const double* B,
+                  int cam_model, const double cam_d[5], int subpix_refinement, const int32_t* search_level, const int32_t* cur_slot, const int32_t* n_steps, const double* B,
                   const double* step, uint8_t* pwb, const float* A_ref_cur, const float* px_ref_pyr, const int32_t* ref_slot,
                   const int32_t* ref_level, const int32_t* mode, double* uv_best, double* px_cur, double* px_scaled, uint8_t* align_active,
                   uint8_t* accepted_raw, int32_t* status) {
@@ -28,7 +30,9 @@ int scan_emulated(int form, int S, const uint8_t* store, long long slot_bytes, i
   a.L.slot_bytes = slot_bytes;
   a.store = store;
   a.cam.fx = cam_k[0]; a.cam.fy = cam_k[1]; a.cam.cx = cam_k[2]; a.cam.cy = cam_k[3];
-  a.cam.width = width; a.cam.height = height; a.cam.model = SVO_HIP_CAM_PINHOLE;
+  a.cam.width = width; a.cam.height = height; a.cam.model = cam_model;
+  for (int k = 0; k < 5; ++k) a.cam.d[k] = cam_d[k];
+  const bool pinhole = cam_model == SVO_HIP_CAM_PINHOLE;
   a.S = S;
   a.opt.subpix_refinement = subpix_refinement;
   a.ws.search_level = const_cast<int32_t*>(search_level);
@@ -56,7 +60,8 @@ int scan_emulated(int form, int S, const uint8_t* store, long long slot_bytes, i
       const int grp = (int)threadIdx.x / 8, lane = (int)threadIdx.x % 8;
       if (grp >= n_groups) return;
       (void)form;
-      epi_scan_seed<true>(a, s0 + grp, lane, boxes[grp].data());
+      if (pinhole) epi_scan_seed<true>(a, s0 + grp, lane, boxes[grp].data());
+      else epi_scan_seed<false>(a, s0 + grp, lane, boxes[grp].data());
     });
   }
   return 0;
