@@ -194,6 +194,145 @@ __device__ __forceinline__ int sym6_rt(int i, int j) {
   return a * 6 - (a * (a - 1)) / 2 + (b - a);
 }
 
+// ---- the per-level arithmetic of a patch ---------------------------------------------------------------------------------
+// H of one patch, J J' summed over its 16 pixels with J = dx a + dy b:
+//     H_p = Sxx aa' + Sxy (ab' + ba') + Syy bb' = [a b] S [a b]'
+// in the factored form: c = Sxx a + Sxy b, d = Sxy a + Syy b, H_p(i,j) = a_i c_j + b_i d_j -- about 50 multiply-adds where
+// the three products per entry written out cost ~150, the same four terms per entry (it differs from the written-out form
+// by rounding only).  a = fl * jac.row(0), b = fl * jac.row(1) of Frame::jacobian_xyz2uv: a[1] and b[0] are zero by construction
+// and are NOT READ.  hp: the packed upper triangle in sym6 order.  A patch that is not part of the sum passes S = 0 and
+// contributes exact zeros.
+template <typename T>
+__host__ __device__ __forceinline__ void sia_patch_hessian(const T a[6], const T b[6], T sxx, T sxy, T syy, T hp[21]) {
+  // column by column: c_j and d_j are used up at once (only a, b and the finished entries stay live)
+  hp[sym6(0, 0)] = a[0] * (sxx * a[0]);
+  hp[sym6(0, 1)] = a[0] * (sxy * b[1]);
+  hp[sym6(1, 1)] = b[1] * (syy * b[1]);
+#pragma unroll
+  for (int j = 2; j < 6; ++j) {
+    const T cj = sxx * a[j] + sxy * b[j];
+    const T dj = sxy * a[j] + syy * b[j];
+    hp[sym6(0, j)] = a[0] * cj;
+    hp[sym6(1, j)] = b[1] * dj;
+#pragma unroll
+    for (int i = 2; i <= j; ++i) hp[sym6(i, j)] = a[i] * cj + b[i] * dj;
+  }
+}
+
+// The bilinear sample, with the order of its one multiplication and three fused multiply-adds spelled out: the template
+// (sia_ref_tile_packed, the scalar block of sia_kernel) and the warped patch (every evaluation) must round alike -- a frame aligned
+// against itself has residuals that are exactly zero -- and left to itself the compiler may fuse a*b + c*d either way
+// round, differently for scalars and for register pairs.
+__device__ __forceinline__ float sia_bilerp(float wtl, float wtr, float wbl, float wbr, float tl, float tr, float bl, float br) {
+  return __builtin_fmaf(wbr, br, __builtin_fmaf(wbl, bl, __builtin_fmaf(wtr, tr, wtl * tl)));
+}
+typedef float sia_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ sia_f2 sia_bilerp2(sia_f2 wtl, sia_f2 wtr, sia_f2 wbl, sia_f2 wbr, sia_f2 tl, sia_f2 tr, sia_f2 bl,
+                                              sia_f2 br) {
+  return __builtin_elementwise_fma(wbr, br, __builtin_elementwise_fma(wbl, bl, __builtin_elementwise_fma(wtr, tr, wtl * tl)));
+}
+
+// bytes [bo, bo+6] of a 12-byte run as the column pairs (0,2) (1,3) (2,4) (3,5) (4,5) (5,6) the packed samples read
+__device__ __forceinline__ void sia_cut_row7_pairs(const uint32_t d[3], uint32_t bo, sia_f2 p[6]) {
+  float w[7];
+  cut_row7(d, bo, w);
+  p[0] = sia_f2{w[0], w[2]};
+  p[1] = sia_f2{w[1], w[3]};
+  p[2] = sia_f2{w[2], w[4]};
+  p[3] = sia_f2{w[3], w[5]};
+  p[4] = sia_f2{w[4], w[5]};
+  p[5] = sia_f2{w[5], w[6]};
+}
+__device__ __forceinline__ float4 sia_f4(sia_f2 a, sia_f2 b) { return make_float4(a.x, a.y, b.x, b.y); }
+
+// precomputeReferencePatches of one patch (sparse_img_align.cpp:84-145) for the packed pixel loop, from its 7 x 7 window
+// (seven 12-byte runs rw, the window's first byte at offset rbo in them, the sub-pixel position su, sv): the 6 x 6
+// neighbourhood of bilinear samples without its corners, handed to store(k, float4) as the eight float4 of the workgroup
+// kernel's LDS tile -- rows 1-4 as the column pairs (0,2) (1,3) (4,5), rows 0 and 5 as (1,3) (2,4) -- and the sums Sxx, Sxy,
+// Syy of the products of the central-difference gradients dx, dy over the 4 x 4 patch.
+// Two columns per instruction: sia_bilerp2 does per sample the operations of sia_bilerp in the same order (the same bits).
+// The gradients are formed two per instruction too and WITHOUT their factor 0.5: it only feeds the three sums, a power of two
+// commutes with every rounding of a 16-term sum (|difference| <= 255: nothing overflows or goes subnormal), so the sums of
+// the unscaled products times 0.25 are the same bits.  The sums keep their order: y outer, x inner, one accumulator each.
+// Rows slide (tile rows r-2, r-1, r are live while row r is sampled; a float4 is stored as soon as its rows exist).
+// acc + a * b of the three sums as the scalar block's `S += dx * dy` is compiled: on the device contracted into one fused
+// multiply-add (every one of its 48 is a v_fmac_f32), on the host (-ffp-contract=off) a product and a sum.  Spelled out,
+// because the compiler does not contract a product it has first put back together from the halves of two register pairs.
+// The first two squares of Sxx and of Syy are the exception: `0 + a0 * a0` folds to the product (a square has no negative
+// zero to lose), and of the two products of a0 * a0 + a1 * a1 the device compiler rounds the SECOND and fuses the first --
+// fma(a0, a0, a1 * a1), where the chain would be fma(a1, a1, a0 * a0).  Sxy's first sum keeps its zero and chains normally.
+#ifdef SVO_HOST_MATH_TEST
+#define SIA_SUM_PRODUCT(a, b, acc) ((acc) + (a) * (b))
+#define SIA_SUM_SQUARES_START(a0, a1) ((a0) * (a0) + (a1) * (a1))
+#else
+#define SIA_SUM_PRODUCT(a, b, acc) __builtin_fmaf((a), (b), (acc))
+#define SIA_SUM_SQUARES_START(a0, a1) __builtin_fmaf((a0), (a0), (a1) * (a1))
+#endif
+template <typename STORE>
+__device__ __forceinline__ void sia_ref_tile_packed(const uint32_t rw[7][3], uint32_t rbo, float su, float sv, STORE&& store,
+                                                    float& Sxx, float& Sxy, float& Syy) {
+  // The reference forms these products in double and rounds to float (:118-121).  u >= 3 here, so su
+  // and sv are multiples of 2^-22: 1-su and 1-sv are exact in f32, and the f32 product of two f32
+  // values is the correctly rounded exact product, like the rounded double product -- bit-identical.
+  const float wtl = (1.f - su) * (1.f - sv);
+  const float wtr = su * (1.f - sv);
+  const float wbl = (1.f - su) * sv;
+  const float wbr = su * sv;
+  const sia_f2 vtl = sia_f2{wtl, wtl}, vtr = sia_f2{wtr, wtr}, vbl = sia_f2{wbl, wbl}, vbr = sia_f2{wbr, wbr};
+  const sia_f2 z2 = sia_f2{0.f, 0.f};
+  float sxx = 0.f, sxy = 0.f, syy = 0.f;
+  sia_f2 wp[6], wn[6];                             // window rows r, r + 1
+  sia_f2 p13 = z2, p24 = z2;                       // tile row r - 2: columns (1,3) (2,4)
+  sia_f2 m02 = z2, m13 = z2, m24 = z2, m45 = z2;   // tile row r - 1
+  sia_cut_row7_pairs(rw[0], rbo, wp);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    sia_cut_row7_pairs(rw[r + 1], rbo, wn);
+    sia_f2 n02 = z2, n13, n24, n45 = z2;  // tile row r
+    if (r == 0 || r == 5) {
+      n13 = sia_bilerp2(vtl, vtr, vbl, vbr, wp[1], wp[2], wn[1], wn[2]);
+      n24 = sia_bilerp2(vtl, vtr, vbl, vbr, wp[2], wp[3], wn[2], wn[3]);
+    } else {
+      n02 = sia_bilerp2(vtl, vtr, vbl, vbr, wp[0], wp[1], wn[0], wn[1]);
+      n13 = sia_bilerp2(vtl, vtr, vbl, vbr, wp[1], wp[2], wn[1], wn[2]);
+      n45 = sia_bilerp2(vtl, vtr, vbl, vbr, wp[4], wp[5], wn[4], wn[5]);
+      n24 = sia_f2{n02.y, n45.x};
+    }
+    if (r == 0) store(0, sia_f4(n13, n24));
+    if (r == 1) store(1, sia_f4(n02, n13));
+    if (r == 2) { store(2, sia_f4(m45, n02)); store(3, sia_f4(n13, n45)); }
+    if (r == 3) store(4, sia_f4(n02, n13));
+    if (r == 4) { store(5, sia_f4(m45, n02)); store(6, sia_f4(n13, n45)); }
+    if (r == 5) store(7, sia_f4(n13, n24));
+    if (r >= 2) {
+      // patch row y = r - 2: dx from tile row r - 1, dy = tile row r minus tile row r - 2 (twice the central differences)
+      const sia_f2 m35 = sia_f2{m13.y, m45.y};
+      const sia_f2 dxa = m24 - m02, dxb = m35 - m13;  // pixels x = 0, 2 and x = 1, 3
+      const sia_f2 dya = n13 - p13, dyb = n24 - p24;
+      const float dx[4] = {dxa.x, dxb.x, dxa.y, dxb.y}, dy[4] = {dya.x, dyb.x, dya.y, dyb.y};
+      if (r == 2) {  // (the sums are zero)
+        sxx = SIA_SUM_SQUARES_START(dx[0], dx[1]);
+        syy = SIA_SUM_SQUARES_START(dy[0], dy[1]);
+        sxy = SIA_SUM_PRODUCT(dx[1], dy[1], SIA_SUM_PRODUCT(dx[0], dy[0], sxy));
+      }
+#pragma unroll
+      for (int x = (r == 2 ? 2 : 0); x < 4; ++x) {
+        sxx = SIA_SUM_PRODUCT(dx[x], dx[x], sxx);
+        sxy = SIA_SUM_PRODUCT(dx[x], dy[x], sxy);
+        syy = SIA_SUM_PRODUCT(dy[x], dy[x], syy);
+      }
+    }
+    p13 = m13; p24 = m24;
+    m02 = n02; m13 = n13; m24 = n24; m45 = n45;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) wp[k] = wn[k];
+    asm volatile("" ::: "memory");  // keeps the compiler from cutting all seven window rows up front
+  }
+  Sxx = 0.25f * sxx;
+  Sxy = 0.25f * sxy;
+  Syy = 0.25f * syy;
+}
+
 // sparse_align_wave.hip
 int launch_sia_wave(const SiaArgs& args, int B, hipStream_t s);
 bool sia_wave_applies(const SiaArgs& args, int B);

@@ -49,7 +49,7 @@ namespace {
 // Waves per SIMD asked of the register allocator.  With the Jacobian products kept inside the iteration
 // loop (see the opaque copies in the H rebuild) and the Gauss-Jordan rebuild the 256-lane instantiation
 // fits 128 VGPRs = 4 waves per SIMD WITH the window cache, i.e. four frames per CU instead of three
-// (1.40 against 1.50 ms on the headline batch); one 8-byte value is spilled once per level.  64/128-lane
+// (1.40 against 1.50 ms on the headline batch); nothing is spilled since the patch Hessian is factored.  64/128-lane
 // workgroups are not limited by registers.  The distorted-camera instantiations (no window cache, the model's
 // world2cam in the loop) stay at 3 waves per SIMD where the workgroup size allows: at 4 they spill 22 dwords.
 // (Five frames per CU -- the reference tile cut to 208 patches, 96 VGPRs -- measured 24 % slower in round 4:
@@ -189,21 +189,10 @@ __device__ __forceinline__ void sia_rebuild_hinv(int lane, int nw, [[maybe_unuse
 
 // DIST: the camera is a distorted model (radial-tangential pinhole or ATAN); the undistorted pinhole
 // keeps its own instantiation so that its inner loop carries no model dispatch.
-// The bilinear sample, with the order of its one multiplication and three fused multiply-adds spelled out: the template
-// (precompute block) and the warped patch (every evaluation, scalar or packed) must round alike -- a frame aligned
-// against itself has residuals that are exactly zero -- and left to itself the compiler may fuse a*b + c*d either way
-// round, differently for scalars and for register pairs.
-__device__ __forceinline__ float sia_bilerp(float wtl, float wtr, float wbl, float wbr, float tl, float tr, float bl, float br) {
-  return __builtin_fmaf(wbr, br, __builtin_fmaf(wbl, bl, __builtin_fmaf(wtr, tr, wtl * tl)));
-}
-typedef float sia_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ sia_f2 sia_bilerp2(sia_f2 wtl, sia_f2 wtr, sia_f2 wbl, sia_f2 wbr, sia_f2 tl, sia_f2 tr, sia_f2 bl,
-                                              sia_f2 br) {
-  return __builtin_elementwise_fma(wbr, br, __builtin_elementwise_fma(wbl, bl, __builtin_elementwise_fma(wtr, tr, wtl * tl)));
-}
+// (The bilinear sample sia_bilerp / sia_bilerp2 of the template and of the warped patch: sia_common.h.)
 
-// SIA_PACKED: the pixel loop of an evaluation on v_pk_*_f32, two pixels per instruction; the reference-width build
-// keeps its f64 sums and the scalar loop.
+// SIA_PACKED: the pixel loop of an evaluation and the template of a level on v_pk_*_f32, two pixels per instruction; the
+// reference-width build keeps its f64 sums and the scalar loops.
 #ifdef SIA_F64_PARTIALS
 #define SIA_PACKED 0
 #else
@@ -368,62 +357,72 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
         vis = true;
         gmask = 1;
         const float su = u_ref - (float)u_i, sv = v_ref - (float)v_i;
-        // The reference forms these products in double and rounds to float (:118-121).  u >= 3 here, so su
-        // and sv are multiples of 2^-22: 1-su and 1-sv are exact in f32, and the f32 product of two f32
-        // values is the correctly rounded exact product, like the rounded double product -- bit-identical.
-        const float wtl = (1.f - su) * (1.f - sv);
-        const float wtr = su * (1.f - sv);
-        const float wbl = (1.f - su) * sv;
-        const float wbr = su * sv;
-        float Bt[6][6];
-        float Wp[7], Wc[7];
         // the 7 x 7 window as 7 runs of 12 bytes, placed inside one tile row of the store where the 7 bytes allow it
         uint32_t rw[7][3];
         const int rxa = run_start(u_i - 3, 7);
         const uint32_t rbo = (uint32_t)(u_i - 3 - rxa);  // 0..5
         load_window12<7>(ref_img, pitch, rxa, v_i - 3, rw);
-        cut_row7(rw[0], rbo, Wp);
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          cut_row7(rw[r + 1], rbo, Wc);
-#pragma unroll
-          for (int c = 0; c < 6; ++c) {
-            const bool need = ((r >= 1 && r <= 4)) || ((c >= 1 && c <= 4));
-            if (need) Bt[r][c] = sia_bilerp(wtl, wtr, wbl, wbr, Wp[c], Wp[c + 1], Wc[c], Wc[c + 1]);
-          }
-#pragma unroll
-          for (int c = 0; c < 7; ++c) Wp[c] = Wc[c];
-        }
-#pragma unroll
-        for (int y = 0; y < 4; ++y)
-#pragma unroll
-          for (int x = 0; x < 4; ++x) {
-            const float dx = 0.5f * (Bt[y + 1][x + 2] - Bt[y + 1][x]);
-            const float dy = 0.5f * (Bt[y + 2][x + 1] - Bt[y][x + 1]);
-            Sxx += (sia_pix)dx * (sia_pix)dx;
-            Sxy += (sia_pix)dx * (sia_pix)dy;
-            Syy += (sia_pix)dy * (sia_pix)dy;
-          }
 #if SIA_PACKED
-        // columns in the order the packed pixel loop pairs them: (0,2) (1,3) (4,5) per row, (1,3) (2,4) in rows 0 and 5
-        s_bt[0][tid] = make_float4(Bt[0][1], Bt[0][3], Bt[0][2], Bt[0][4]);
-        s_bt[1][tid] = make_float4(Bt[1][0], Bt[1][2], Bt[1][1], Bt[1][3]);
-        s_bt[2][tid] = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][2]);
-        s_bt[3][tid] = make_float4(Bt[2][1], Bt[2][3], Bt[2][4], Bt[2][5]);
-        s_bt[4][tid] = make_float4(Bt[3][0], Bt[3][2], Bt[3][1], Bt[3][3]);
-        s_bt[5][tid] = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][2]);
-        s_bt[6][tid] = make_float4(Bt[4][1], Bt[4][3], Bt[4][4], Bt[4][5]);
-        s_bt[7][tid] = make_float4(Bt[5][1], Bt[5][3], Bt[5][2], Bt[5][4]);
-#else
-        s_bt[0][tid] = make_float4(Bt[0][1], Bt[0][2], Bt[0][3], Bt[0][4]);
-        s_bt[1][tid] = make_float4(Bt[1][0], Bt[1][1], Bt[1][2], Bt[1][3]);
-        s_bt[2][tid] = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][1]);
-        s_bt[3][tid] = make_float4(Bt[2][2], Bt[2][3], Bt[2][4], Bt[2][5]);
-        s_bt[4][tid] = make_float4(Bt[3][0], Bt[3][1], Bt[3][2], Bt[3][3]);
-        s_bt[5][tid] = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][1]);
-        s_bt[6][tid] = make_float4(Bt[4][2], Bt[4][3], Bt[4][4], Bt[4][5]);
-        s_bt[7][tid] = make_float4(Bt[5][1], Bt[5][2], Bt[5][3], Bt[5][4]);
+        // The interpolated tile, columns in the order the packed pixel loop pairs them -- (0,2) (1,3) (4,5) per row, (1,3) (2,4)
+        // in rows 0 and 5 -- and the gradient sums, two samples per instruction (sia_common.h): the same bits as the scalar
+        // block below.  Only in the window-cache instantiations (the headline's 256 lanes, 4 waves per SIMD): the register
+        // pairs cost the others spills (the distorted-camera ones: 0 -> 36 bytes of scratch) or a wave per SIMD (128 lanes).
+        if constexpr (WC) {
+          sia_ref_tile_packed(rw, rbo, su, sv, [&](int k, float4 v) { s_bt[k][tid] = v; }, Sxx, Sxy, Syy);
+        } else
 #endif
+        {
+          // The reference forms these products in double and rounds to float (:118-121).  u >= 3 here, so su
+          // and sv are multiples of 2^-22: 1-su and 1-sv are exact in f32, and the f32 product of two f32
+          // values is the correctly rounded exact product, like the rounded double product -- bit-identical.
+          const float wtl = (1.f - su) * (1.f - sv);
+          const float wtr = su * (1.f - sv);
+          const float wbl = (1.f - su) * sv;
+          const float wbr = su * sv;
+          float Bt[6][6];
+          float Wp[7], Wc[7];
+          cut_row7(rw[0], rbo, Wp);
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            cut_row7(rw[r + 1], rbo, Wc);
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+              const bool need = ((r >= 1 && r <= 4)) || ((c >= 1 && c <= 4));
+              if (need) Bt[r][c] = sia_bilerp(wtl, wtr, wbl, wbr, Wp[c], Wp[c + 1], Wc[c], Wc[c + 1]);
+            }
+#pragma unroll
+            for (int c = 0; c < 7; ++c) Wp[c] = Wc[c];
+          }
+#pragma unroll
+          for (int y = 0; y < 4; ++y)
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+              const float dx = 0.5f * (Bt[y + 1][x + 2] - Bt[y + 1][x]);
+              const float dy = 0.5f * (Bt[y + 2][x + 1] - Bt[y][x + 1]);
+              Sxx += (sia_pix)dx * (sia_pix)dx;
+              Sxy += (sia_pix)dx * (sia_pix)dy;
+              Syy += (sia_pix)dy * (sia_pix)dy;
+            }
+#if SIA_PACKED
+          s_bt[0][tid] = make_float4(Bt[0][1], Bt[0][3], Bt[0][2], Bt[0][4]);
+          s_bt[1][tid] = make_float4(Bt[1][0], Bt[1][2], Bt[1][1], Bt[1][3]);
+          s_bt[2][tid] = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][2]);
+          s_bt[3][tid] = make_float4(Bt[2][1], Bt[2][3], Bt[2][4], Bt[2][5]);
+          s_bt[4][tid] = make_float4(Bt[3][0], Bt[3][2], Bt[3][1], Bt[3][3]);
+          s_bt[5][tid] = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][2]);
+          s_bt[6][tid] = make_float4(Bt[4][1], Bt[4][3], Bt[4][4], Bt[4][5]);
+          s_bt[7][tid] = make_float4(Bt[5][1], Bt[5][3], Bt[5][2], Bt[5][4]);
+#else
+          s_bt[0][tid] = make_float4(Bt[0][1], Bt[0][2], Bt[0][3], Bt[0][4]);
+          s_bt[1][tid] = make_float4(Bt[1][0], Bt[1][1], Bt[1][2], Bt[1][3]);
+          s_bt[2][tid] = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][1]);
+          s_bt[3][tid] = make_float4(Bt[2][2], Bt[2][3], Bt[2][4], Bt[2][5]);
+          s_bt[4][tid] = make_float4(Bt[3][0], Bt[3][1], Bt[3][2], Bt[3][3]);
+          s_bt[5][tid] = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][1]);
+          s_bt[6][tid] = make_float4(Bt[4][2], Bt[4][3], Bt[4][4], Bt[4][5]);
+          s_bt[7][tid] = make_float4(Bt[5][1], Bt[5][2], Bt[5][3], Bt[5][4]);
+#endif
+        }
       } else {
         // jacobian_cache_.setZero() (:64): the J columns of a feature skipped here
         // stay zero; a stale ref_patch_cache_ row (if any) is kept
@@ -708,22 +707,18 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
       SIA_ACC(2, tb0, tb1);
       if (changed) {
         // the set of patches inside the current image changed: rebuild H.
-        // H += J J' summed over the patch = Sxx aa' + Sxy (ab'+ba') + Syy bb'
-        // (opaque copies: otherwise the ~60 products below, all invariant in the iteration loop, are hoisted
+        // H += J J' summed over the patch = Sxx aa' + Sxy (ab'+ba') + Syy bb' = [a b] S [a b]' (sia_patch_hessian)
+        // (opaque copies: otherwise the products below, all invariant in the iteration loop, are hoisted
         // out of it and stay live across it -- 35 VGPRs, the difference between 3 and 4 waves per SIMD)
         sia_acc zi_ = zi, xn_ = xn, yn_ = yn;
         asm volatile("" : "+v"(zi_), "+v"(xn_), "+v"(yn_));
         const sia_acc one = 1, zero = 0;
         const sia_acc ja[6] = {-zi_ * fl, zero, xn_ * zi_ * fl, xn_ * yn_ * fl, -(one + xn_ * xn_) * fl, yn_ * fl};
         const sia_acc jb[6] = {zero, -zi_ * fl, yn_ * zi_ * fl, (one + yn_ * yn_) * fl, -xn_ * yn_ * fl, -xn_ * fl};
+        // a patch outside the current image: S = 0, exact zeros in every entry
+        const sia_acc sxx = m ? (sia_acc)Sxx : zero, sxy = m ? (sia_acc)Sxy : zero, syy = m ? (sia_acc)Syy : zero;
         sia_acc hp[24];
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-          for (int j = i; j < 6; ++j) {
-            const sia_acc v = (sia_acc)Sxx * (ja[i] * ja[j]) + (sia_acc)Sxy * (ja[i] * jb[j] + jb[i] * ja[j]) + (sia_acc)Syy * (jb[i] * jb[j]);
-            hp[sym6(i, j)] = m ? v : zero;
-          }
+        sia_patch_hessian<sia_acc>(ja, jb, sxx, sxy, syy, hp);
         hp[21] = hp[22] = hp[23] = zero;
 #pragma unroll
         for (int g = 0; g < 3; ++g) {

@@ -429,13 +429,11 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
           asm volatile("" : "+v"(zi), "+v"(xn), "+v"(yn));  // or the ~60 products below are hoisted out of the loop, per patch
           const float ja[6] = {-zi * fl, 0.f, xn * zi * fl, xn * yn * fl, -(1.f + xn * xn) * fl, yn * fl};
           const float jb[6] = {0.f, -zi * fl, yn * zi * fl, (1.f + yn * yn) * fl, -xn * yn * fl, -xn * fl};
+          // (a patch outside the current image: S = 0, exact zeros)
+          float hk[21];
+          sia_patch_hessian<float>(ja, jb, m ? p.Sxx : 0.f, m ? p.Sxy : 0.f, m ? p.Syy : 0.f, hk);
 #pragma unroll
-          for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int j = i; j < 6; ++j) {
-              const float v = p.Sxx * (ja[i] * ja[j]) + p.Sxy * (ja[i] * jb[j] + jb[i] * ja[j]) + p.Syy * (jb[i] * jb[j]);
-              hp[sym6(i, j)] += m ? v : 0.f;
-            }
+          for (int j = 0; j < 21; ++j) hp[j] += hk[j];
           p.inH = (int)m;
         }
 #pragma unroll
