@@ -111,6 +111,23 @@ def build_ref(force: bool = False) -> bool:
     return ref_available()
 
 
+def build_ref_harness(harness, units, name):
+    """-> the path of build/<name>/lib<name>.so: the test harness `harness` (a tests/host/ref_*.cpp) compiled against oracle/shim
+    together with the reference's own svo/src/<unit>.cpp, where they lie, with the flags of the Makefile's reference build
+    (contraction off, as written); None where the reference checkout lacks one of the units"""
+    root = os.path.dirname(HERE)
+    srcs = [os.path.join(REFERENCE_ROOT, "svo", "src", u + ".cpp") for u in units]
+    if not all(os.path.exists(s) for s in srcs):
+        return None
+    lib_path = os.path.join(root, "build", name, f"lib{name}.so")
+    os.makedirs(os.path.dirname(lib_path), exist_ok=True)
+    if not os.path.exists(lib_path) or os.path.getmtime(lib_path) < max(os.path.getmtime(s) for s in srcs + [harness]):
+        subprocess.run([os.environ.get("CXX", "g++"), "-O3", "-std=c++11", "-fPIC", "-w", "-fno-math-errno", "-ffp-contract=off", "-pthread",
+                        "-I", os.path.join(HERE, "shim"), "-I", HERE, "-I", os.path.join(REFERENCE_ROOT, "svo", "include"), "-shared",
+                        "-Wl,--no-undefined", harness, *srcs, "-o", lib_path, "-lm", "-lpthread"], check=True)
+    return lib_path
+
+
 class Track:
     def __init__(self, which: str = "orc"):
         assert which in ("orc", "ref")

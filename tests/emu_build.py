@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE.  The host-emulated build of the C-ABI library: the .hip translation units of rpg_svo_amd/csrc compiled by
 ROCm's clang++ as plain C++ through tests/host/hip_emu.h (work-items as fibers, barriers, LDS, cross-lane rendezvous) and
 linked into build/emu/libsvo_hip_emulated[_<defines>][_<sanitizer>].so: ONE library with every kernel family, the entry points of
-libsvo_hip.so's kernel files on host memory; no timing.  Also K10's stand-alone sanitizer program, compiled with the same flags."""
+libsvo_hip.so's kernel files on host memory; no timing.  Also THE recipe of a stand-alone sanitizer program (build_program,
+run_program): emulated units and a main of their own, compiled with the same flags."""
 import ctypes as C
 import glob
 import os
@@ -11,7 +12,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNITS = ("common", "pyramid", "map_mirror", "matcher", "feature_align", "depth_filter", "sparse_align", "sparse_align_wave",
-         "pose_optimizer_wave", "pose_optimizer", "point_optimizer", "fast_detect", "klt_track", "homography_init", "first_map")
+         "pose_optimizer_wave", "pose_optimizer", "point_optimizer", "fast_detect", "klt_track", "homography_init", "first_map",
+         "frame_close")
 
 
 # Compile-time variants of the library the emulated parity tests run on besides the default build (round 4 queued ten of
@@ -91,7 +93,8 @@ def _kernel_deps():
         [os.path.join(ROOT, "include", "svo_hip.h"), os.path.join(ROOT, "tests", "host", "hip_emu.h")]
 
 
-def build_emulated(defines=()):
+def build_emulated(defines=(), bind=()):
+    """-> a fresh CDLL of the emulated library built with `defines`; the entries named in `bind` get capi.PROTOTYPES' prototypes"""
     # SVO_EMU_EXTRA_DEFINES="A B": added to every emulated build of the run (e.g. the whole round-5 queue on the default tests)
     from rpg_svo_amd.build import DEFAULT_DEFINES   # (the default library's own flags: the emulated default build has them too)
     defines = tuple(dict.fromkeys(tuple(DEFAULT_DEFINES) + tuple(defines) + tuple(os.environ.get("SVO_EMU_EXTRA_DEFINES", "").split())))
@@ -129,21 +132,39 @@ def build_emulated(defines=()):
             list(ex.map(lambda cmd: subprocess.run(cmd, check=True), todo))
     if not os.path.exists(lib_path) or any(os.path.getmtime(o) > os.path.getmtime(lib_path) for o in objs):
         subprocess.run([cxx, "-shared", *san_flags, "-o", lib_path, *objs], check=True)
-    lib = C.CDLL(lib_path)
+    lib = C.CDLL(lib_path)   # (a CDLL object of the caller's own: argtypes belong to the object, and other callers pass raw pointers)
+    if bind:
+        from rpg_svo_amd import capi
+        for name in bind:
+            getattr(lib, name).restype, getattr(lib, name).argtypes = capi.PROTOTYPES[name]
     return lib
 
 
-def build_first_map_asan_program():
-    """-> the path of build/emu/first_map_asan: K10's emulated units and tests/host/first_map_asan_main.cpp, one executable
-    instrumented with AddressSanitizer and UndefinedBehaviorSanitizer (a program of its own: nothing is loaded into Python)"""
+def build_program(name, sources, sanitize=True, extra_checks=(), deps=()):
+    """-> the path of build/emu/<name>: the files `sources` of tests/host (emulated units and a *_main.cpp) compiled with the
+    library's flags into one executable, instrumented with AddressSanitizer and UndefinedBehaviorSanitizer unless `sanitize` is
+    False (a program of its own: nothing is loaded into Python).  `extra_checks`: further -fsanitize= groups; `deps`: what it is
+    rebuilt after besides its sources, the kernel files and this file (names in tests/host, or paths)."""
     from rpg_svo_amd.build import DEFAULT_DEFINES
     cxx = _cxx()
     if not os.path.exists(cxx):
         pytest.skip("no ROCm clang++ to compile the kernels for the host")
-    exe = os.path.join(ROOT, "build", "emu", "first_map_asan")
+    exe = os.path.join(ROOT, "build", "emu", name)
     os.makedirs(os.path.dirname(exe), exist_ok=True)
-    srcs = [os.path.join(ROOT, "tests", "host", f) for f in ("emu_tu_common.cpp", "emu_tu_first_map.cpp", "first_map_asan_main.cpp")]
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in [*srcs, *_kernel_deps(), os.path.abspath(__file__)]):
-        subprocess.run([cxx, *_kernel_cxxflags(DEFAULT_DEFINES), "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-fno-sanitize=vptr,function", "-fno-omit-frame-pointer", "-g", *srcs, "-o", exe], check=True)
+    host = os.path.join(ROOT, "tests", "host")
+    srcs = [os.path.join(host, f) for f in sources]
+    after = [*srcs, *_kernel_deps(), os.path.abspath(__file__), *[os.path.join(host, d) for d in deps]]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in after):
+        san = ["-fsanitize=address,undefined", *[f"-fsanitize={c}" for c in extra_checks], "-fno-sanitize-recover=undefined",
+               "-fno-sanitize=vptr,function", "-fno-omit-frame-pointer", "-g"] if sanitize else []
+        subprocess.run([cxx, *_kernel_cxxflags(DEFAULT_DEFINES), *san, *srcs, "-o", exe], check=True)
     return exe
+
+
+def run_program(exe, *args):
+    """runs a program of build_program: no sanitizer report, exit code 0, last line "ok" -> the finished process"""
+    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=600, env={"ASAN_OPTIONS": "detect_leaks=0"})
+    print(r.stdout)
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-4000:], r.stderr[-2000:])
+    return r

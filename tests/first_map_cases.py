@@ -1,13 +1,13 @@
 """TEST INFRASTRUCTURE.  The cases of the K10 tests (numpy only): what K8 / K9 and the gates leave for n sequences, built by
 hand so that every rule of svo_hip_first_map / svo_hip_initialize_seeds (include/svo_hip.h) is exercised on the smallest
 shapes at which it can go wrong; the checker's answer per batch (tests/first_map_checker.py, computed once per process);
-the two comparison rules.
+the comparison rule of the GPU tests.
 
 Corners that are not point_ok carry NaN points, NaN bearings and pixels of -777: nothing of theirs may be read.  Pixels are
 f32; poses are random rotations of up to 3 rad, so all four branches of the quaternion conversion occur.
 
-Comparison: `compare_bits` -- every output bit for bit (the emulated kernel; the reference's arithmetic is IEEE f64 with one
-rounding per operation, and so is the emulation's).  `compare_device` -- the GPU rule: discrete outputs equal, f64 ones
+Comparison: `compare_bits` of tests/host_buffers.py -- every output bit for bit (the emulated kernel; the reference's arithmetic
+is IEEE f64 with one rounding per operation, and so is the emulation's).  `compare_device` -- the GPU rule: discrete outputs equal, f64 ones
 within 1e-14 relative (each value is a chain of under ten IEEE operations: about 45 ulp of headroom), f32 seed fields within
 1 ulp; returns the largest differences so that the tests can print them."""
 import functools
@@ -17,6 +17,7 @@ import numpy as np
 
 import first_map_checker as chk
 from homography_cases import rodrigues
+from host_buffers import relative_difference, same_bits
 
 INPUTS = ("result", "point_ok", "point_w", "px_ref", "px_cur", "f_ref", "f_cur", "T_ref_w", "T_cur_w")
 DISCRETE = ("n_points", "src_index", "key_pts", "occupancy")
@@ -205,29 +206,6 @@ def out_shapes(n_seq, n_pts, cells):
                 px=((n_seq, 2, n_pts, 2), np.float64), f=((n_seq, 2, n_pts, 3), np.float64), key_pts=((n_seq, 2, 5), np.int32),
                 depth_mean=((n_seq,), np.float64), depth_min=((n_seq,), np.float64), xyz_ref=((n_seq, n_pts, 3), np.float64),
                 occupancy=((n_seq, cells), np.uint8))
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def compare_bits(got, want, what=""):
-    for k, w in want.items():
-        g = np.asarray(got[k])
-        assert same_bits(g, np.asarray(w, g.dtype).reshape(g.shape)), (what, k)
-
-
-def relative_difference(got, want):
-    """the largest |got - want| / max(|want|, tiny) over the elements; equal bits (NaN and infinities included) count as 0"""
-    g, w = np.asarray(got, np.float64).ravel(), np.asarray(want, np.float64).ravel()
-    same = (g == w) | (np.isnan(g) & np.isnan(w))
-    if same.all():
-        return 0.0
-    with np.errstate(all="ignore"):
-        d = np.abs(g - w) / np.maximum(np.abs(w), np.finfo(np.float64).tiny)
-    d = np.where(same, 0.0, d)
-    return float(np.inf if np.isnan(d).any() else d.max())
 
 
 def ulp_difference(got, want):

@@ -4,8 +4,8 @@ shapes at which it can go wrong, and the checker's answer per batch (tests/frame
 
 Rows without a point carry NaN positions and NaN bearings; rows beyond n carry has_point = 1, NaN everywhere and pixels of
 -777; keyframes beyond n_kf carry NaN poses and overlap 0: nothing of theirs may be read.  Poses are random rotations of up to
-3 rad, so all four branches of the quaternion conversion occur.  The comparison rules are tests/first_map_cases.py's
-(compare_bits for the emulation, compare_device for the GPU: discrete outputs equal, f64 within 1e-14 relative -- the values
+3 rad, so all four branches of the quaternion conversion occur.  The comparison rules are K10's
+(host_buffers.compare_bits for the emulation, first_map_cases.compare_device for the GPU: discrete outputs equal, f64 within 1e-14 relative -- the values
 are K10's chains of under ten IEEE operations)."""
 import functools
 import types

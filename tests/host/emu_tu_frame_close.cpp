@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: rpg_svo_amd/csrc/frame_close.hip compiled for the host (tests/host/hip_emu.h); with emu_tu_common.cpp
-// the emulated library of K11 and its stand-alone sanitizer program (tests/emu_build_frame_close.py builds both).
+// TEST INFRASTRUCTURE: rpg_svo_amd/csrc/frame_close.hip compiled for the host (tests/host/hip_emu.h); a unit of the emulated
+// library, and with emu_tu_common.cpp of K11's stand-alone sanitizer program (tests/emu_build.py builds both).
 #include "hip_emu.h"
 #include "../../rpg_svo_amd/csrc/frame_close.hip"

@@ -2,7 +2,7 @@
 // form (emu_tu_frame_close.cpp, emu_tu_common.cpp) on heap buffers of exactly the sizes the C ABI asks for: 257 and 1024 rows
 // per sequence with 64 keyframes, four sequences each whose row counts lie below, at and beyond the stride (and below zero),
 // rows without a point, pixels that are NaN, negative and beyond the grid, keyframe counts of 0, 10, 64 and beyond the stride.
-// Built with -fsanitize=address,undefined by tests/emu_build_frame_close.py: a load or store outside a buffer, or undefined
+// Built with -fsanitize=address,undefined by tests/emu_build.py: a load or store outside a buffer, or undefined
 // behaviour in the kernel, stops it with a report and a non-zero exit status.  Exits 0 when both calls return SVO_HIP_OK with
 // the point counts the inputs were made for.
 #include <cmath>

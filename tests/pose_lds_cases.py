@@ -138,31 +138,7 @@ def check(row, want, T, Cov, stats, ran, hp_out):
     return devs
 
 
-# ---- the stand-alone sanitizer program (tests/host/pose_lds_asan_main.cpp): builder, input file, output file ------------------
-def build_asan_program():
-    """-> the path of build/emu/pose_lds_asan: the emulated pose optimizer (both kernels) with exactly sized dynamic LDS and
-    tests/host/pose_lds_asan_main.cpp, one executable instrumented with AddressSanitizer and UndefinedBehaviorSanitizer (a
-    program of its own: nothing is loaded into Python).  The flags are those of emu_build.build_first_map_asan_program."""
-    import os
-    import subprocess
-    import pytest
-    import emu_build
-    from rpg_svo_amd.build import DEFAULT_DEFINES
-    cxx = emu_build._cxx()
-    if not os.path.exists(cxx):
-        pytest.skip("no ROCm clang++ to compile the kernels for the host")
-    exe = os.path.join(emu_build.ROOT, "build", "emu", "pose_lds_asan")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    host = os.path.join(emu_build.ROOT, "tests", "host")
-    srcs = [os.path.join(host, f) for f in ("emu_tu_common.cpp", "pose_lds_asan_tu_wave.cpp", "pose_lds_asan_tu_ordered.cpp",
-                                            "pose_lds_asan_main.cpp")]
-    deps = [*srcs, os.path.join(host, "pose_lds_asan_lds.h"), *emu_build._kernel_deps(), os.path.abspath(__file__)]
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
-        subprocess.run([cxx, *emu_build._kernel_cxxflags(DEFAULT_DEFINES), "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-fno-sanitize=vptr,function", "-fno-omit-frame-pointer", "-g", *srcs, "-o", exe], check=True)
-    return exe
-
-
+# ---- the stand-alone sanitizer program (tests/host/pose_lds_asan_main.cpp): input file, output file ---------------------------
 def write_rows(path, scene, rows):
     from rpg_svo_amd import capi
     c = lambda a, dt: np.ascontiguousarray(a, dtype=dt).tobytes()

@@ -27,6 +27,7 @@ import torch
 
 import first_map_cases as cases
 import first_map_checker as chk
+from host_buffers import relative_difference
 import klt_scenes
 from test_klt_gpu import make_store
 
@@ -115,7 +116,7 @@ def test_two_images_to_a_state_that_tracking_runs_on(gpu_device):
     torch.cuda.synchronize()
     T_dev, T_host = get(on_device.T_cur_from_ref), get(on_host.T_cur_from_ref)
     d = float(se3.log_norm(T_dev, T_host).max())
-    depth_diff = cases.relative_difference(got["xyz_ref"][0, :n_points], xyz_host[:n_points])
+    depth_diff = relative_difference(got["xyz_ref"][0, :n_points], xyz_host[:n_points])
     print(f"K1 on the first map: n_tracked {int(on_device.n_tracked[0])} (host-marshalled {int(on_host.n_tracked[0])}), SE(3) log-norm between "
           f"the two poses {d:.2e}; xyz_ref against numpy's norm {depth_diff:.2e} relative")
     assert int(on_device.n_tracked[0]) == int(on_host.n_tracked[0]) > 0

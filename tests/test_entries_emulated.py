@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from helpers import camera_models
+from host_buffers import ptr
 from oracle import pytrack
 from rpg_svo_amd import capi, se3, synth
 
@@ -31,16 +32,12 @@ def scene():
     return synth.make_track_scene(n_kf=4, n_feat=100, cam=camera_models()["pinhole"])
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)  # (the pointer object keeps the array alive)
-
-
 def _store(emu, images, n_levels=5):
     imgs = np.ascontiguousarray(images)
     n, h, w = imgs.shape
     layout = capi.pyr_layout(w, h, n_levels)
     buf = np.zeros(capi.pyr_store_bytes(layout, n), np.uint8)
-    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), _p(buf), 0, n, _p(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
+    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), ptr(buf), 0, n, ptr(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
     return layout, buf
 
 
@@ -72,20 +69,20 @@ def test_emulated_align_batch_and_its_phased_form(emu, oracle, scene):
 
     def run(entry, extra):
         px, ok, h_inv = px0.copy(), np.zeros(M, np.int32), np.zeros(M)
-        rc = getattr(emu, entry)(C.byref(layout), _p(store), M, _p(slot), _p(level), _p(pwb), _p(dirs), _p(use_1d), n_iter, _p(px), _p(ok),
-                                 _p(h_inv), *extra, None)
+        rc = getattr(emu, entry)(C.byref(layout), ptr(store), M, ptr(slot), ptr(level), ptr(pwb), ptr(dirs), ptr(use_1d), n_iter, ptr(px), ptr(ok),
+                                 ptr(h_inv), *extra, None)
         assert rc == 0, (entry, rc)
         return px, ok, h_inv
 
     px_a, ok_a, h_a = run("svo_hip_align_batch", ())
     ev_c = np.zeros(M, np.int32)
-    px_c, ok_c, h_c = run("svo_hip_align_batch_counted", (_p(ev_c),))
+    px_c, ok_c, h_c = run("svo_hip_align_batch_counted", (ptr(ev_c),))
     emu.svo_hip_align_workspace_bytes.restype = C.c_size_t
     need = emu.svo_hip_align_workspace_bytes(M)
     assert need > 0                                                     # (the emulated build's threshold: the phased path)
     raw, ev_p = np.full(need + 512, 0xFF, np.uint8), np.zeros(M, np.int32)
     ws = raw[(-raw.ctypes.data) % 256:][:need + 256]                     # (the entry wants 256-byte alignment, like hipMalloc's)
-    px_p, ok_p, h_p = run("svo_hip_align_batch_phased", (_p(ev_p), _p(ws), C.c_size_t(ws.size)))
+    px_p, ok_p, h_p = run("svo_hip_align_batch_phased", (ptr(ev_p), ptr(ws), C.c_size_t(ws.size)))
     for px, ok, h in ((px_c, ok_c, h_c), (px_p, ok_p, h_p)):
         assert np.array_equal(ok, ok_a) and np.array_equal(px.view(np.uint64), px_a.view(np.uint64))
         assert np.array_equal(h.view(np.uint64), h_a.view(np.uint64))
@@ -142,8 +139,8 @@ def test_emulated_wave_alignment_iteration_caps_and_borders(emu, oracle, scene, 
             uu, vv = rng.integers(8, w - 8), rng.integers(8, h - 8)     # a template from somewhere else
             pwb[t] = img[vv - 5:vv + 5, uu - 5:uu + 5].ravel()
     px, ok, h_inv, ev = px0.copy(), np.zeros(M, np.int32), np.zeros(M), np.full(M, -1, np.int32)
-    rc = emu.svo_hip_align_batch_counted(C.byref(layout), _p(store), M, _p(slot), _p(level), _p(pwb), _p(dirs), _p(use_1d), n_iter, _p(px),
-                                         _p(ok), _p(h_inv), _p(ev), None)
+    rc = emu.svo_hip_align_batch_counted(C.byref(layout), ptr(store), M, ptr(slot), ptr(level), ptr(pwb), ptr(dirs), ptr(use_1d), n_iter, ptr(px),
+                                         ptr(ok), ptr(h_inv), ptr(ev), None)
     assert rc == 0
     assert ev.min() >= 0 and ev.max() <= n_iter and (n_iter == 0 or (ev == 0).sum() >= M // 8)
     for t in range(M):
@@ -190,8 +187,8 @@ def test_emulated_find_epipolar_match_direct(emu, oracle, scene):
     for align_1d in (0, 1):
         o_ = capi.DepthFilterOptions(0, 0, 0.0, int(align_1d), 10, 1000, 1, 1, 5, 0.7)
         ok, depth, px, lvl = np.zeros(S, np.int32), np.zeros(S), np.zeros((S, 2)), np.zeros(S, np.int32)
-        rc = emu.svo_hip_find_epipolar_match_direct(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), S, _p(cur), C.byref(ftr), _p(de),
-                                                    _p(dmin), _p(dmax), C.byref(o_), _p(ok), _p(depth), _p(px), _p(lvl), _p(ws),
+        rc = emu.svo_hip_find_epipolar_match_direct(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), S, ptr(cur), C.byref(ftr), ptr(de),
+                                                    ptr(dmin), ptr(dmax), C.byref(o_), ptr(ok), ptr(depth), ptr(px), ptr(lvl), ptr(ws),
                                                     C.c_size_t(ws.size), None)
         assert rc == 0, rc
         opt = pytrack.matcher_options(n_pyr_levels=5, align_1d=align_1d)
@@ -224,7 +221,7 @@ def test_emulated_update_seed_and_compute_tau_batches(emu, oracle):
     a, b, mu = c([s.a for s in seeds], np.float32), c([s.b for s in seeds], np.float32), c([s.mu for s in seeds], np.float32)
     zr, s2, bid = c([s.z_range for s in seeds], np.float32), c([s.sigma2 for s in seeds], np.float32), np.zeros(S, np.int32)
     ss = capi.Seeds(a.ctypes.data, b.ctypes.data, mu.ctypes.data, zr.ctypes.data, s2.ctypes.data, bid.ctypes.data)
-    assert emu.svo_hip_update_seed_batch(S, _p(x), _p(tau2), C.byref(ss), None) == 0
+    assert emu.svo_hip_update_seed_batch(S, ptr(x), ptr(tau2), C.byref(ss), None) == 0
     got = np.stack([a, b, mu, s2], axis=1).astype(np.float64)
     want = np.array([[n.a, n.b, n.mu, n.sigma2] for n in (orc.update_seed(x[i], tau2[i], seeds[i]) for i in range(S))])
     fin = np.isfinite(want).all(axis=1)
@@ -244,7 +241,7 @@ def test_emulated_update_seed_and_compute_tau_batches(emu, oracle):
     ang = np.arctan(1.0 / (2.0 * 315.5)) * 2.0
     tau = np.zeros(n)
     t_rc, f = np.ascontiguousarray(t_rc), np.ascontiguousarray(f)
-    assert emu.svo_hip_compute_tau_batch(n, _p(t_rc), _p(f), _p(z), C.c_double(ang), _p(tau), None) == 0
+    assert emu.svo_hip_compute_tau_batch(n, ptr(t_rc), ptr(f), ptr(z), C.c_double(ang), ptr(tau), None) == 0
     for i in range(n):
         T = np.concatenate([np.eye(3).ravel(), t_rc[i]])
         want_tau = orc.compute_tau(T, f[i], z[i], ang)
@@ -270,8 +267,8 @@ def test_emulated_select_matches_compose_poses_cam2world(emu_default, oracle, ki
         cap = max(M, 1)
         n, sel, f = np.zeros(1, np.int32), np.zeros(cap, np.int32), np.zeros((cap, 3))
         lvl, p, has = np.zeros(cap, np.int32), np.zeros((cap, 3)), np.zeros(cap, np.uint8)
-        rc = emu.svo_hip_select_matches(C.byref(cs), M, _p(cell), _p(ok), _p(px), _p(level), _p(pos), max_fts, _p(n), _p(sel), _p(f), _p(lvl),
-                                        _p(p), _p(has), None, 0, None)
+        rc = emu.svo_hip_select_matches(C.byref(cs), M, ptr(cell), ptr(ok), ptr(px), ptr(level), ptr(pos), max_fts, ptr(n), ptr(sel), ptr(f), ptr(lvl),
+                                        ptr(p), ptr(has), None, 0, None)
         assert rc == 0, rc
         k = int(n[0])
         assert k == len(sel_o)
@@ -284,15 +281,15 @@ def test_emulated_select_matches_compose_poses_cam2world(emu_default, oracle, ki
     A = np.stack([se3.exp(rng.normal(size=6) * 0.3) for _ in range(n)])
     B = np.stack([se3.exp(rng.normal(size=6) * 0.3) for _ in range(n)])
     out = np.zeros((n, 12))
-    assert emu.svo_hip_compose_poses(n, _p(A), _p(B), _p(out), None, None) == 0
+    assert emu.svo_hip_compose_poses(n, ptr(A), ptr(B), ptr(out), None, None) == 0
     assert np.abs(out - se3.mul(A, B)).max() < 1e-14
     idx = rng.permutation(n).astype(np.int32)
     out2 = np.zeros((n, 12))
-    assert emu.svo_hip_compose_poses(n, _p(A), _p(B), _p(out2), _p(idx), None) == 0
+    assert emu.svo_hip_compose_poses(n, ptr(A), ptr(B), ptr(out2), ptr(idx), None) == 0
     assert np.array_equal(out2[idx], out)
     px = np.ascontiguousarray(np.stack([rng.uniform(0, cam.width, n), rng.uniform(0, cam.height, n)], axis=1))
     fb = np.zeros((n, 3))
-    assert emu.svo_hip_cam2world(C.byref(cs), n, _p(px), _p(fb), None) == 0
+    assert emu.svo_hip_cam2world(C.byref(cs), n, ptr(px), ptr(fb), None) == 0
     assert np.abs(fb - synth._bearing(cam, px)).max() < 1e-14
 
 
@@ -436,12 +433,12 @@ def test_emulated_frame_pose_compose_is_the_hosts_product(emu_default):
     rng = np.random.default_rng(5)
     for T, q, t in frame_pose_compose_cases(rng):
         table = np.zeros((3, 12)); copy = np.zeros(12); out = np.zeros(12); sig = np.zeros(1, np.int32)
-        assert emu.svo_hip_frame_pose_compose(_p(T), _p(q), _p(t), _p(table), 1, _p(copy), _p(out), None, 0, 0, None, None, 0, None, None,
-                                              _p(sig), 7, None) == 0
+        assert emu.svo_hip_frame_pose_compose(ptr(T), ptr(q), ptr(t), ptr(table), 1, ptr(copy), ptr(out), None, 0, 0, None, None, 0, None, None,
+                                              ptr(sig), 7, None) == 0
         want = _host_frame_pose(T, q, t)
         assert np.array_equal(table[1], want) and np.array_equal(copy, want) and np.array_equal(out, want) and sig[0] == 7
         assert not table[0].any() and not table[2].any()
-    assert emu.svo_hip_frame_pose_compose(None, _p(q), _p(t), _p(table), 1, None, None, None, 0, 0, None, None, 0, None, None, None, 0,
+    assert emu.svo_hip_frame_pose_compose(None, ptr(q), ptr(t), ptr(table), 1, None, None, None, 0, 0, None, None, 0, None, None, None, 0,
                                           None) == -1  # SVO_HIP_EINVAL
     # the ranking, on the undistorted pinhole (the distorted models' projection has its own bit-exact tests)
     cam = camera_models()["pinhole"]
@@ -452,8 +449,8 @@ def test_emulated_frame_pose_compose_is_the_hosts_product(emu_default):
         T = np.ascontiguousarray(se3.exp(rng.normal(size=6) * 0.05)); q = rng.normal(size=4); q /= np.linalg.norm(q); t = rng.normal(size=3) * 0.2
         for max_n in (3, 10):
             tab = table.copy(); rank = np.full(n_tab, 99, np.int32); rank2 = np.full(n_tab, 99, np.int32)
-            assert emu.svo_hip_frame_pose_compose(_p(T), _p(q), _p(t), _p(tab), n_tab - 2, None, None, C.byref(cs), n_tab, n_kf, _p(key_pos),
-                                                  _p(key_valid), max_n, _p(rank), _p(rank2), None, 0, None) == 0
+            assert emu.svo_hip_frame_pose_compose(ptr(T), ptr(q), ptr(t), ptr(tab), n_tab - 2, None, None, C.byref(cs), n_tab, n_kf, ptr(key_pos),
+                                                  ptr(key_valid), max_n, ptr(rank), ptr(rank2), None, 0, None) == 0
             want = host_keyframe_ranks(cam, _host_frame_pose(T, q, t), _composed_quat(T, q), key_pos, key_valid, tab, n_kf, max_n)
             assert np.array_equal(rank, want) and np.array_equal(rank2, want), (trial, rank, want)
             assert (rank[n_kf:] == -1).all() and rank.max() < max_n and rank[7] == -1
@@ -473,10 +470,10 @@ def test_emulated_indirect_match_batch_is_the_direct_one(emu, scene):
     slots = np.arange(T.shape[0], dtype=np.int32)
     frames = capi.Frames(T.shape[0], 0, slots.ctypes.data, T.ctypes.data)
     M = len(scene.obs)
-    ptr = np.zeros(M + 1, np.int32)
+    obs_ptr = np.zeros(M + 1, np.int32)
     flat = []
     for i, o in enumerate(scene.obs):
-        ptr[i + 1] = ptr[i] + len(o)
+        obs_ptr[i + 1] = obs_ptr[i] + len(o)
         flat.extend(o)
     c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
     o_frame, o_level = c([o[0] for o in flat], np.int32), c([o[3] for o in flat], np.int32)
@@ -495,16 +492,16 @@ def test_emulated_indirect_match_batch_is_the_direct_one(emu, scene):
 
     ref = outputs(M, 0)
     ws = np.full(emu.svo_hip_match_workspace_bytes(cap) + 256, 0xFF, np.uint8)   # (poisoned: NaN / -1 to whoever reads scratch it did not write)
-    rc = emu.svo_hip_find_match_direct(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), M, _p(cur), _p(pos), _p(ptr), C.byref(obs),
-                                       5, 10, _p(ref["px"]), _p(ref["ok"]), _p(ref["ref_obs"]), _p(ref["sl"]), _p(ref["A"]), _p(ref["patches"]),
-                                       _p(ws), C.c_size_t(ws.size), None)
+    rc = emu.svo_hip_find_match_direct(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), M, ptr(cur), ptr(pos), ptr(obs_ptr), C.byref(obs),
+                                       5, 10, ptr(ref["px"]), ptr(ref["ok"]), ptr(ref["ref_obs"]), ptr(ref["sl"]), ptr(ref["A"]), ptr(ref["patches"]),
+                                       ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     res = outputs(cap, -7)
     d_M = np.array([M], np.int32)
-    ob_begin, ob_end, cur_p, pos_p = pad(ptr[:-1].copy()), pad(ptr[1:].copy()), pad(cur), pad(pos)
-    rc = emu.svo_hip_find_match_direct_indirect(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), cap, _p(d_M), _p(cur_p), _p(pos_p),
-                                                _p(ob_begin), _p(ob_end), C.byref(obs), 5, 10, _p(res["px"]), _p(res["ok"]), _p(res["ref_obs"]),
-                                                _p(res["sl"]), _p(res["A"]), _p(res["patches"]), _p(ws), C.c_size_t(ws.size), None)
+    ob_begin, ob_end, cur_p, pos_p = pad(obs_ptr[:-1].copy()), pad(obs_ptr[1:].copy()), pad(cur), pad(pos)
+    rc = emu.svo_hip_find_match_direct_indirect(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), cap, ptr(d_M), ptr(cur_p), ptr(pos_p),
+                                                ptr(ob_begin), ptr(ob_end), C.byref(obs), 5, 10, ptr(res["px"]), ptr(res["ok"]), ptr(res["ref_obs"]),
+                                                ptr(res["sl"]), ptr(res["A"]), ptr(res["patches"]), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     for k in ref:
         assert np.array_equal(res[k][:M], ref[k]), k
@@ -516,11 +513,11 @@ def test_emulated_indirect_match_batch_is_the_direct_one(emu, scene):
         n, sel = np.zeros(1, np.int32), np.full(121, -1, np.int32)
         f, pos_o, lvl_o, has = np.zeros((121, 3)), np.zeros((121, 3)), np.zeros(121, np.int32), np.zeros(121, np.uint8)
         if indirect:
-            rc = emu.svo_hip_select_matches_indirect(C.byref(cam), cap, _p(d_M), _p(cell_p), _p(res["ok"]), _p(res["px"]), _p(res["sl"]),
-                                                     _p(pos_p), 120, _p(n), _p(sel), _p(f), _p(lvl_o), _p(pos_o), _p(has), None, 0, None)
+            rc = emu.svo_hip_select_matches_indirect(C.byref(cam), cap, ptr(d_M), ptr(cell_p), ptr(res["ok"]), ptr(res["px"]), ptr(res["sl"]),
+                                                     ptr(pos_p), 120, ptr(n), ptr(sel), ptr(f), ptr(lvl_o), ptr(pos_o), ptr(has), None, 0, None)
         else:
-            rc = emu.svo_hip_select_matches(C.byref(cam), M, _p(cell), _p(ref["ok"]), _p(ref["px"]), _p(ref["sl"]), _p(pos), 120, _p(n),
-                                            _p(sel), _p(f), _p(lvl_o), _p(pos_o), _p(has), None, 0, None)
+            rc = emu.svo_hip_select_matches(C.byref(cam), M, ptr(cell), ptr(ref["ok"]), ptr(ref["px"]), ptr(ref["sl"]), ptr(pos), 120, ptr(n),
+                                            ptr(sel), ptr(f), ptr(lvl_o), ptr(pos_o), ptr(has), None, 0, None)
         assert rc == 0, rc
         outs.append((n, sel, f, lvl_o, pos_o, has))
     for a, b in zip(*outs):

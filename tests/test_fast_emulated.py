@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from host_buffers import ptr
 from oracle import pytrack
 from rpg_svo_amd import capi, synth
 from helpers import FUZZ, fuzz_rng
@@ -18,24 +19,20 @@ def emu():
     return build_emulated(())
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)  # (the pointer object keeps the array alive)
-
-
 def detect(emu, imgs, n_pyr, levels, cell, occ, thresh=20.0):
     n, h, w = imgs.shape
     layout = capi.pyr_layout(w, h, n_pyr)
     store = np.zeros(capi.pyr_store_bytes(layout, n), np.uint8)
     imgs = np.ascontiguousarray(imgs)
-    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), _p(store), 0, n, _p(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
+    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), ptr(store), 0, n, ptr(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
     cols, rows = -(-w // cell), -(-h // cell)
     nc = cols * rows
     emu.svo_hip_fast_workspace_bytes.restype = C.c_size_t
     ws = np.full(emu.svo_hip_fast_workspace_bytes(C.byref(layout), n, nc), 0xFF, np.uint8)   # (poisoned: NaN / -1 to whoever reads scratch it did not write)
     slots = np.arange(n, dtype=np.int32)
     xy, lvl, sc = np.zeros((n, nc, 2), np.int32), np.zeros((n, nc), np.int32), np.zeros((n, nc), np.float32)
-    rc = emu.svo_hip_fast_detect(C.byref(layout), _p(store), n, _p(slots), levels, 20, cell, cols, rows, None if occ is None else _p(occ),
-                                 C.c_double(thresh), _p(xy), _p(lvl), _p(sc), _p(ws), C.c_size_t(ws.size), None)
+    rc = emu.svo_hip_fast_detect(C.byref(layout), ptr(store), n, ptr(slots), levels, 20, cell, cols, rows, None if occ is None else ptr(occ),
+                                 C.c_double(thresh), ptr(xy), ptr(lvl), ptr(sc), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     return xy, lvl, sc, cols, rows
 

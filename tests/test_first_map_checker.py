@@ -11,14 +11,14 @@ the reference library of oracle/ is built they are compared with its Seed constr
 Measured: 0 differences over the 28 batches (88 sequences, 11 of them without SUCCESS or without a point), all four cameras."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import first_map_cases as cases
 import first_map_checker as chk
-from oracle.pytrack import REFERENCE_ROOT as REFERENCE
+from host_buffers import same_bits
+from oracle.pytrack import build_ref_harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_UNITS = ("frame", "point", "config", "feature_detection")
@@ -26,17 +26,9 @@ REF_UNITS = ("frame", "point", "config", "feature_detection")
 
 @pytest.fixture(scope="module")
 def ref():
-    srcs = [os.path.join(REFERENCE, "svo", "src", u + ".cpp") for u in REF_UNITS]
-    if not all(os.path.exists(s) for s in srcs):
+    lib_path = build_ref_harness(os.path.join(ROOT, "tests", "host", "ref_first_map.cpp"), REF_UNITS, "ref_first_map")
+    if lib_path is None:
         pytest.skip("no reference checkout to compile frame.cpp / feature_detection.cpp from")
-    harness = os.path.join(ROOT, "tests", "host", "ref_first_map.cpp")
-    lib_path = os.path.join(ROOT, "build", "ref_first_map", "libref_first_map.so")
-    os.makedirs(os.path.dirname(lib_path), exist_ok=True)
-    if not os.path.exists(lib_path) or os.path.getmtime(lib_path) < max(os.path.getmtime(s) for s in srcs + [harness]):
-        oracle = os.path.join(ROOT, "oracle")   # (the flags of oracle/Makefile's reference build: contraction off, as written)
-        subprocess.run([os.environ.get("CXX", "g++"), "-O3", "-std=c++11", "-fPIC", "-w", "-fno-math-errno", "-ffp-contract=off", "-pthread",
-                        "-I", os.path.join(oracle, "shim"), "-I", oracle, "-I", os.path.join(REFERENCE, "svo", "include"), "-shared",
-                        "-Wl,--no-undefined", harness, *srcs, "-o", lib_path, "-lm", "-lpthread"], check=True)
     lib = C.CDLL(lib_path)
     lib.ref_first_map.restype = C.c_int
     lib.ref_first_map.argtypes = [C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3
@@ -68,7 +60,7 @@ def test_checker_has_the_references_bits(ref, name):
         assert np.array_equal(key_pts, e["key_pts"][i]), (name, i, key_pts, e["key_pts"][i])
         assert np.array_equal(occ, e["occupancy"][i]), (name, i)
         if n:   # (the reference leaves both unset without a point; the library defines 0, 0)
-            assert cases.same_bits(scene, np.array([e["depth_mean"][i], e["depth_min"][i]])), (name, i, scene)
+            assert same_bits(scene, np.array([e["depth_mean"][i], e["depth_min"][i]])), (name, i, scene)
 
 
 def test_seed_fields_are_the_reference_constructors():
@@ -84,8 +76,8 @@ def test_seed_fields_are_the_reference_constructors():
             n = int(c.expect["n_seeds"][fr])
             for k in ("a", "b", "mu", "z_range", "sigma2"):
                 want = np.float32(getattr(r, k))
-                assert cases.same_bits(np.float32(getattr(a, k)), want), (name, fr, k)
-                assert all(cases.same_bits(v, want) for v in c.expect[k][fr, :n]), (name, fr, k)
+                assert same_bits(np.float32(getattr(a, k)), want), (name, fr, k)
+                assert all(same_bits(v, want) for v in c.expect[k][fr, :n]), (name, fr, k)
 
 
 def test_the_stated_differences_outside_the_grid(ref):

@@ -13,47 +13,14 @@ import pytest
 
 import first_map_cases as cases
 import first_map_checker as chk
+from host_buffers import Guarded, compare_bits, ptr, same_bits
 from rpg_svo_amd import capi
-
-GUARD = 64          # elements of 0xA5 bytes on either side of every output
 
 
 @pytest.fixture(scope="module")
 def emu():
     from emu_build import build_emulated
-    lib = build_emulated(())   # (a CDLL object of this module's own; the cases pass addresses as ints, which need the argtypes)
-    for name in ("svo_hip_first_map", "svo_hip_initialize_seeds"):
-        getattr(lib, name).restype, getattr(lib, name).argtypes = capi.PROTOTYPES[name]
-    return lib
-
-
-class Guarded:
-    """name -> poisoned array between two guard bands"""
-
-    def __init__(self, shapes):
-        self.raw, self.view = {}, {}
-        for k, (shape, dt) in shapes.items():
-            n = int(np.prod(shape))
-            raw = np.full((n + 2 * GUARD) * np.dtype(dt).itemsize, 0xA5, np.uint8)
-            v = raw.view(dt)[GUARD:GUARD + n].reshape(shape)
-            v[...] = np.nan if np.issubdtype(dt, np.floating) else 0x55
-            self.raw[k], self.view[k] = raw, v
-
-    def ptr(self, k):
-        return self.view[k].ctypes.data if self.view[k].size else self.raw[k].ctypes.data + GUARD * self.view[k].dtype.itemsize
-
-    def guards_intact(self):
-        for k, raw in self.raw.items():
-            g = GUARD * self.view[k].dtype.itemsize
-            assert (raw[:g] == 0xA5).all() and (raw[len(raw) - g:] == 0xA5).all(), k
-        return True
-
-    def untouched(self):
-        return all(np.isnan(v).all() if np.issubdtype(v.dtype, np.floating) else (v == 0x55).all() for v in self.view.values())
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return build_emulated((), bind=("svo_hip_first_map", "svo_hip_initialize_seeds"))   # (the cases pass addresses as ints, which need the argtypes)
 
 
 def call_first_map(emu, b, n_seq=None, n_pts=None, override=(), grid=None, cells=None):
@@ -65,7 +32,7 @@ def call_first_map(emu, b, n_seq=None, n_pts=None, override=(), grid=None, cells
     cells = n_cols * n_rows if cells is None else cells
     out = Guarded(cases.out_shapes(max(n_seq, 0), max(n_pts, 0), max(cells, 0)))
     o = capi.FirstMapOut(*[out.ptr(k) for k in capi.FIRST_MAP_OUTPUTS])
-    args = dict(cam=C.byref(capi.camera(b.cam)), out=C.byref(o), **{k: _p(inp[k]) for k in cases.INPUTS})
+    args = dict(cam=C.byref(capi.camera(b.cam)), out=C.byref(o), **{k: ptr(inp[k]) for k in cases.INPUTS})
     args.update(dict(override))
     rc = emu.svo_hip_first_map(args["cam"], n_seq, n_pts, *[args[k] for k in cases.INPUTS], cell_size, n_cols, n_rows, cells, args["out"], None)
     return rc, out
@@ -76,8 +43,8 @@ def call_seeds(emu, c, stride, batch_id, n_frames=None, n_cells=None, override=(
     n_cells = c.n_cells if n_cells is None else n_cells
     out = Guarded(chk.seed_out_shapes(max(n_frames, 0), max(stride, 0)))
     o = capi.SeedInitOut(*[out.ptr(k) if optional or k not in ("type", "grad") else None for k in capi.SEED_INIT_OUTPUTS])
-    args = dict(cam=C.byref(capi.camera(c.cam)), xy=_p(c.xy), level=_p(c.level), score=_p(c.score), frame_index=_p(c.frame_index),
-                depth_mean=_p(c.depth_mean), depth_min=_p(c.depth_min), out=C.byref(o))
+    args = dict(cam=C.byref(capi.camera(c.cam)), xy=ptr(c.xy), level=ptr(c.level), score=ptr(c.score), frame_index=ptr(c.frame_index),
+                depth_mean=ptr(c.depth_mean), depth_min=ptr(c.depth_min), out=C.byref(o))
     args.update(dict(override))
     rc = emu.svo_hip_initialize_seeds(args["cam"], n_frames, n_cells, args["xy"], args["level"], args["score"], c.threshold, args["frame_index"],
                                       args["depth_mean"], args["depth_min"], batch_id, stride, args["out"], None)
@@ -89,7 +56,7 @@ def test_first_map_has_the_checkers_bits(emu, name):
     b = cases.batches()[name]
     rc, out = call_first_map(emu, b)
     assert rc == 0 and out.guards_intact()
-    cases.compare_bits(out.view, b.expect, name)   # (the outputs started poisoned: equal bits also mean every element was written)
+    compare_bits(out.view, b.expect, name)   # (the outputs started poisoned: equal bits also mean every element was written)
 
 
 def test_what_the_cases_cover():
@@ -128,9 +95,9 @@ def test_identical_sequences_and_repeated_calls_give_the_same_bits(emu):
         _, one = call_first_map(emu, b)
         _, two = call_first_map(emu, b)
         for k in one.view:
-            assert cases.same_bits(one.view[k], two.view[k]), k
+            assert same_bits(one.view[k], two.view[k]), k
             for j in twins[1:]:
-                assert cases.same_bits(one.view[k][twins[0]], one.view[k][j]), (k, j)
+                assert same_bits(one.view[k][twins[0]], one.view[k][j]), (k, j)
 
 
 def test_first_map_limits_and_error_codes(emu):
@@ -159,7 +126,7 @@ def test_seeds_have_the_checkers_bits(emu, name):
     c, stride, batch_id = cases.seed_cases()[name]
     rc, out = call_seeds(emu, c, stride, batch_id)
     assert rc == 0 and out.guards_intact()
-    cases.compare_bits(out.view, c.expect, name)
+    compare_bits(out.view, c.expect, name)
     n = c.expect["n_seeds"]
     assert (n == (c.score > c.threshold).sum(axis=1)).all()
     if name == "no_corner":
@@ -175,7 +142,7 @@ def test_seeds_have_the_checkers_bits(emu, name):
         if k in ("type", "grad"):
             assert (bare.view[k] == 0x55).all() if k == "type" else np.isnan(bare.view[k]).all()
         else:
-            assert cases.same_bits(bare.view[k], out.view[k]), k
+            assert same_bits(bare.view[k], out.view[k]), k
 
 
 def test_seed_limits_and_error_codes(emu):

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import first_map_cases as cases
+from host_buffers import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -73,9 +74,9 @@ def test_identical_sequences_and_repeated_calls_give_the_same_bits(gpu_device):
         b = cases.batches()[name]
         one, two = run_first_map(gpu_device, b), run_first_map(gpu_device, b)
         for k in one:
-            assert cases.same_bits(one[k], two[k]), k
+            assert same_bits(one[k], two[k]), k
             for j in twins[1:]:
-                assert cases.same_bits(one[k][twins[0]], one[k][j]), (k, j)
+                assert same_bits(one[k][twins[0]], one[k][j]), (k, j)
 
 
 def test_limits_and_error_codes(gpu_device):
@@ -156,4 +157,4 @@ def test_a_graph_of_the_whole_bootstrap_replays_the_eager_bits(gpu_device):
         graph.replay()
         torch.cuda.synchronize()
         for n, v in held.items():
-            assert cases.same_bits(v.cpu().numpy(), eager[n]), n
+            assert same_bits(v.cpu().numpy(), eager[n]), n

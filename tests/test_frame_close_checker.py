@@ -13,16 +13,15 @@ needNewKf and setTrackingQuality are members of FrameHandlerMono / FrameHandlerB
 Measured: 0 differences over the 30 batches without out-of-grid pixels; the furthest keyframe over all 34."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import frame_close_cases as cases
 import frame_close_checker as chk
-from first_map_cases import same_bits
 from first_map_checker import frame_pos, se3_from_Rt
-from oracle.pytrack import REFERENCE_ROOT as REFERENCE
+from host_buffers import same_bits
+from oracle.pytrack import build_ref_harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_UNITS = ("frame", "point", "config", "feature_detection", "map")
@@ -30,17 +29,9 @@ REF_UNITS = ("frame", "point", "config", "feature_detection", "map")
 
 @pytest.fixture(scope="module")
 def ref():
-    srcs = [os.path.join(REFERENCE, "svo", "src", u + ".cpp") for u in REF_UNITS]
-    if not all(os.path.exists(s) for s in srcs):
+    lib_path = build_ref_harness(os.path.join(ROOT, "tests", "host", "ref_frame_close.cpp"), REF_UNITS, "ref_frame_close")
+    if lib_path is None:
         pytest.skip("no reference checkout to compile frame.cpp / feature_detection.cpp / map.cpp from")
-    harness = os.path.join(ROOT, "tests", "host", "ref_frame_close.cpp")
-    lib_path = os.path.join(ROOT, "build", "ref_frame_close", "libref_frame_close.so")
-    os.makedirs(os.path.dirname(lib_path), exist_ok=True)
-    if not os.path.exists(lib_path) or os.path.getmtime(lib_path) < max(os.path.getmtime(s) for s in srcs + [harness]):
-        oracle = os.path.join(ROOT, "oracle")   # (the flags of oracle/Makefile's reference build: contraction off, as written)
-        subprocess.run([os.environ.get("CXX", "g++"), "-O3", "-std=c++11", "-fPIC", "-w", "-fno-math-errno", "-ffp-contract=off", "-pthread",
-                        "-I", os.path.join(oracle, "shim"), "-I", oracle, "-I", os.path.join(REFERENCE, "svo", "include"), "-shared",
-                        "-Wl,--no-undefined", harness, *srcs, "-o", lib_path, "-lm", "-lpthread"], check=True)
     lib = C.CDLL(lib_path)
     lib.ref_frame_close.restype = C.c_int
     lib.ref_frame_close.argtypes = [C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 3

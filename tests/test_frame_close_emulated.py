@@ -1,4 +1,4 @@
-"""svo_hip_frame_close (K11, csrc/frame_close.hip) of the host-emulated build (tests/emu_build_frame_close.py: the kernel
+"""svo_hip_frame_close (K11, csrc/frame_close.hip) of the host-emulated build (tests/emu_build.py: the kernel
 compiled for the CPU through tests/host/hip_emu.h, one fiber per work-item, the LDS atomics as host atomics) on the cases of
 tests/frame_close_cases.py against the sequential checker (tests/frame_close_checker.py): EVERY output bit for bit.  Every
 output buffer lies between two guard bands and starts poisoned: whatever the entry defines it must write, and nothing else.
@@ -17,21 +17,17 @@ import pytest
 
 import frame_close_cases as cases
 import frame_close_checker as chk
-from first_map_cases import compare_bits, same_bits
+from host_buffers import Guarded, compare_bits, ptr, same_bits
 from rpg_svo_amd import capi
-from test_first_map_emulated import Guarded
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+ENTRIES = ("svo_hip_frame_close", "svo_hip_frame_close_params_default")
 
 
 @pytest.fixture(scope="module")
 def emu():
-    from emu_build_frame_close import build_frame_close_emulated
-    return build_frame_close_emulated()
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    from emu_build import build_emulated
+    return build_emulated((), bind=ENTRIES)
 
 
 def call(emu, b, B=None, n_stride=None, kf_stride=None, grid=None, cells=None, override=(), drop_in=(), drop_out=()):
@@ -43,7 +39,7 @@ def call(emu, b, B=None, n_stride=None, kf_stride=None, grid=None, cells=None, o
     cell_size, n_cols, n_rows = b.grid if grid is None else grid
     cells = n_cols * n_rows if cells is None else cells
     out = Guarded(cases.out_shapes(max(B, 0), max(min(n_stride, b.n_stride), 0), max(cells, 0)))
-    i = capi.FrameCloseIn(*[None if k in drop_in else _p(inp[k]) for k in capi.FRAME_CLOSE_INPUTS])
+    i = capi.FrameCloseIn(*[None if k in drop_in else ptr(inp[k]) for k in capi.FRAME_CLOSE_INPUTS])
     o = capi.FrameCloseOut(*[None if k in drop_out else out.ptr(k) for k in capi.FRAME_CLOSE_OUTPUTS])
     args = dict(cam=C.byref(capi.camera(b.cam)), inp=C.byref(i), params=C.byref(cases.params_struct(capi, b.params)), out=C.byref(o))
     args.update(dict(override))
@@ -61,8 +57,8 @@ def test_frame_close_has_the_checkers_bits(emu, name):
 
 def run_every_case():
     """(what the schedule test runs in a child process) -> the number of batches compared"""
-    from emu_build_frame_close import build_frame_close_emulated
-    emu = build_frame_close_emulated()
+    from emu_build import build_emulated
+    emu = build_emulated((), bind=ENTRIES)
     for name in cases.NAMES:
         b = cases.batches()[name]
         rc, out = call(emu, b)

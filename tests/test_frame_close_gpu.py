@@ -15,7 +15,8 @@ import pytest
 import torch
 
 import frame_close_cases as cases
-from first_map_cases import compare_device, same_bits
+from first_map_cases import compare_device
+from host_buffers import same_bits
 
 pytestmark = pytest.mark.gpu
 

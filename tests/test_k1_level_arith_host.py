@@ -6,36 +6,12 @@ without loading anything into Python: tests/host/k1_level_arith_main.cpp is a pr
       positions 0 and 1 - 2^-22, constant windows, checkerboards of 0 / 255).
 Built with the emulated library's compile flags, once plain and once with -fsanitize=address,undefined; it must exit 0, its
 last line "ok", with no report."""
-import os
-import subprocess
-
 import pytest
 
-import emu_build
-
-ROOT = emu_build.ROOT
-
-
-def _build(sanitized):
-    from rpg_svo_amd.build import DEFAULT_DEFINES
-    cxx = emu_build._cxx()
-    if not os.path.exists(cxx):
-        pytest.skip("no ROCm clang++ to compile the kernels' headers for the host")
-    exe = os.path.join(ROOT, "build", "emu", "k1_level_arith" + ("_asan" if sanitized else ""))
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    src = os.path.join(ROOT, "tests", "host", "k1_level_arith_main.cpp")
-    deps = [src, os.path.abspath(__file__), *emu_build._kernel_deps()]
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
-        san = ["-fsanitize=address,undefined", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=undefined",
-               "-fno-sanitize=vptr,function", "-fno-omit-frame-pointer", "-g"] if sanitized else []
-        subprocess.run([cxx, *emu_build._kernel_cxxflags(DEFAULT_DEFINES), *san, src, "-o", exe], check=True)
-    return exe
+from emu_build import build_program, run_program
 
 
 @pytest.mark.parametrize("sanitized", [False, True], ids=["plain", "address_undefined"])
 def test_patch_hessian_and_packed_template(sanitized):
-    exe = _build(sanitized)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env={"ASAN_OPTIONS": "detect_leaks=0"})
-    print(r.stdout)
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-4000:], r.stderr[-2000:])
+    run_program(build_program("k1_level_arith" + ("_asan" if sanitized else ""), ("k1_level_arith_main.cpp",), sanitize=sanitized,
+                              extra_checks=("float-cast-overflow",), deps=(__file__,)))

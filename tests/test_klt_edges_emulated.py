@@ -17,8 +17,9 @@ import pytest
 
 import klt_edge_cases as cases
 from helpers import camera_models, CAMERA_KINDS
+from host_buffers import ptr
 from rpg_svo_amd import capi
-from test_klt_emulated import _p, build_store, default_params, klt_track
+from test_klt_emulated import build_store, default_params, klt_track
 
 
 @pytest.fixture(scope="module")
@@ -81,8 +82,8 @@ def test_summary_sizes_and_parities(emu, kind, n_pts):
     n_pairs = len(st)
     f, d = np.full((n_pairs, n_pts, 3), np.nan), np.full((n_pairs, n_pts), np.nan)
     n, med = np.full(n_pairs, -1, np.int32), np.full(n_pairs, np.nan)
-    assert emu.svo_hip_klt_summarize(C.byref(ccam), n_pairs, n_pts, _p(px_ref), _p(px_cur), _p(st), _p(f), _p(d), _p(n), _p(med), None) == 0
+    assert emu.svo_hip_klt_summarize(C.byref(ccam), n_pairs, n_pts, ptr(px_ref), ptr(px_cur), ptr(st), ptr(f), ptr(d), ptr(n), ptr(med), None) == 0
     f_ref = np.zeros((n_pairs, n_pts, 3))
     px64 = np.ascontiguousarray(px_cur.reshape(-1, 2).astype(np.float64))
-    assert emu.svo_hip_cam2world(C.byref(ccam), n_pairs * n_pts, _p(px64), _p(f_ref), None) == 0
+    assert emu.svo_hip_cam2world(C.byref(ccam), n_pairs * n_pts, ptr(px64), ptr(f_ref), None) == 0
     cases.verify_summary(px_ref, px_cur, st, f, d, n, med, f_ref)

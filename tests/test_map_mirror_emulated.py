@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from helpers import camera_models, FUZZ, fuzz_rng, oracle_reproject_map, random_map
+from host_buffers import ptr
 from rpg_svo_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,10 +21,6 @@ def emu(request):
     from emu_build import build_emulated
     from emu_build import BUILDS
     return build_emulated(BUILDS[request.param])
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data
 
 
 class HostMirror:
@@ -70,7 +67,7 @@ class HostMirror:
         if self.pending is not None:
             p, n_pts, n_obs = self.pending
             self.pending = None
-            g = lambda k: _ptr(p.get(k))
+            g = lambda k: ptr(p.get(k))
             patch = capi.MapPatch(n_pts, n_obs, g("index"), g("pos"), g("type"), g("order"), g("obs_begin"), g("obs_count"), g("obs_index"),
                                   g("obs_order"), capi.Features(g("obs_frame"), g("obs_level"), g("obs_type"), g("obs_px"), g("obs_f"), g("obs_grad")))
         frames = capi.Frames(n_frames, 0, None, T.ctypes.data)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import FUZZ, camera_models, fuzz_rng
+from host_buffers import ptr
 from oracle import pytrack
 from rpg_svo_amd import capi, se3, synth
 
@@ -31,10 +32,6 @@ def scene(request):
     return synth.make_track_scene(n_kf=4, n_feat=100, cam=camera_models()[request.param], seed=777 + FUZZ)
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)  # (the pointer object keeps the array alive)
-
-
 def pose_optimize(emu, cam, n, f, level, pos, hp, T0, thresh, n_iter, entry="svo_hip_pose_optimize"):
     c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
     n, f, level, pos = c(n, np.int32), c(f, np.float64), c(level, np.int32), c(pos, np.float64)
@@ -42,8 +39,8 @@ def pose_optimize(emu, cam, n, f, level, pos, hp, T0, thresh, n_iter, entry="svo
     T, hpo = c(T0, np.float64).copy(), c(hp, np.uint8).copy()
     Cov, stats, ran = np.zeros((B, 36)), np.zeros((B, 4)), np.zeros(B, np.int32)
     cs = capi.camera(cam)
-    rc = getattr(emu, entry)(C.byref(cs), B, _p(n), ns, _p(f), _p(level), _p(pos), _p(hpo), C.c_double(thresh), n_iter, _p(T), _p(Cov),
-                             _p(stats), _p(ran), None)
+    rc = getattr(emu, entry)(C.byref(cs), B, ptr(n), ns, ptr(f), ptr(level), ptr(pos), ptr(hpo), C.c_double(thresh), n_iter, ptr(T), ptr(Cov),
+                             ptr(stats), ptr(ran), None)
     assert rc == 0, rc
     return T, Cov, stats, ran, hpo
 
@@ -136,20 +133,20 @@ def test_emulated_point_optimize(emu_default, oracle, scene):
     T = np.ascontiguousarray(scene.T_f_w)
     slots = np.arange(T.shape[0], dtype=np.int32)
     frames = capi.Frames(T.shape[0], 0, slots.ctypes.data, T.ctypes.data)
-    ptr = np.zeros(len(scene.obs) + 1, dtype=np.int32)
+    obs_ptr = np.zeros(len(scene.obs) + 1, dtype=np.int32)
     fr, ff = [], []
     for i, o in enumerate(scene.obs):
-        ptr[i + 1] = ptr[i] + len(o)
+        obs_ptr[i + 1] = obs_ptr[i] + len(o)
         for x in o:
             fr.append(x[0])
             ff.append(x[2] + rng.normal(size=3) * 1e-3)
     fr, ff = np.array(fr, np.int32), np.ascontiguousarray(ff, dtype=np.float64)
     p0 = scene.pt_pos + rng.normal(size=scene.pt_pos.shape) * 0.05
     out = np.ascontiguousarray(p0).copy()
-    assert emu.svo_hip_point_optimize(C.byref(frames), len(scene.obs), _p(ptr), _p(fr), _p(ff), 5, _p(out), None) == 0
+    assert emu.svo_hip_point_optimize(C.byref(frames), len(scene.obs), ptr(obs_ptr), ptr(fr), ptr(ff), 5, ptr(out), None) == 0
     for i in range(0, len(scene.obs), 3):
         Ti = np.array([scene.T_f_w[x[0]] for x in scene.obs[i]])
-        o = orc.point_optimize(Ti, ff[ptr[i]:ptr[i + 1]], p0[i], 5)
+        o = orc.point_optimize(Ti, ff[obs_ptr[i]:obs_ptr[i + 1]], p0[i], 5)
         assert np.abs(o - out[i]).max() < 1e-11, i
 
 
@@ -164,7 +161,7 @@ def test_emulated_reproject_points(emu_default, oracle, scene):
     pos = np.ascontiguousarray(scene.pt_pos, dtype=np.float64)
     cell, px = np.zeros(P, np.int32), np.zeros((P, 2))
     cs = capi.camera(scene.cam)
-    assert emu.svo_hip_reproject_points(C.byref(cs), C.byref(frames), P, _p(cur), _p(pos), 30, 22, _p(cell), _p(px), None) == 0
+    assert emu.svo_hip_reproject_points(C.byref(cs), C.byref(frames), P, ptr(cur), ptr(pos), 30, 22, ptr(cell), ptr(px), None) == 0
     for i in range(P):
         k, p = orc.reproject_point(scene.cam, scene.T_f_w[scene.cur], scene.pt_pos[i], 30, 22)
         assert k == cell[i] and np.abs(p - px[i]).max() < 1e-10

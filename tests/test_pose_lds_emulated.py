@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import pose_lds_cases as cases
+from host_buffers import ptr
 from oracle import pytrack
 from rpg_svo_amd import capi
 
@@ -23,10 +24,6 @@ def scene():
     return cases.make_scene()
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def run(emu, scene, row, n_iter, entry="svo_hip_pose_optimize"):
     B, ns = cases.B, row["ns"]
     c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
@@ -35,8 +32,8 @@ def run(emu, scene, row, n_iter, entry="svo_hip_pose_optimize"):
     T, hp = row["T0"].copy(), row["hp"].copy()
     Cov, stats, ran = np.zeros((B, 36)), np.zeros((B, 4)), np.full(B, -1, np.int32)
     cs = capi.camera(scene.cam)
-    rc = getattr(emu, entry)(C.byref(cs), B, _p(n), ns, _p(f), _p(level), _p(pos), _p(hp), C.c_double(cases.THRESH), n_iter, _p(T),
-                             _p(Cov), _p(stats), _p(ran), None)
+    rc = getattr(emu, entry)(C.byref(cs), B, ptr(n), ns, ptr(f), ptr(level), ptr(pos), ptr(hp), C.c_double(cases.THRESH), n_iter, ptr(T),
+                             ptr(Cov), ptr(stats), ptr(ran), None)
     assert rc == 0, rc
     return T, Cov, stats, ran, hp
 

@@ -4,24 +4,21 @@ tests/pose_lds_cases.py through the host-emulated svo_hip_pose_optimize and svo_
 with its observations compacted into LDS, the ordered kernel behind it) on heap buffers of exactly the documented sizes and
 on dynamic LDS of exactly each launch's byte count.  It must exit 0 with no report, and what it computed is held against the
 oracle like the emulated library's results."""
-import subprocess
-
 import numpy as np
 
 import pose_lds_cases as cases
+from emu_build import build_program, run_program
 from oracle import pytrack
 
 
 def test_pose_optimizer_stays_inside_its_buffers_and_its_lds(oracle, tmp_path):
-    exe = cases.build_asan_program()
+    # (both kernels of the emulated pose optimizer, with exactly sized dynamic LDS: tests/host/pose_lds_asan_lds.h)
+    exe = build_program("pose_lds_asan", ("emu_tu_common.cpp", "pose_lds_asan_tu_wave.cpp", "pose_lds_asan_tu_ordered.cpp", "pose_lds_asan_main.cpp"),
+                        deps=("pose_lds_asan_lds.h", cases.__file__))
     scene = cases.make_scene()
     rows = [cases.make_row(scene, ns) for ns in cases.ROWS]
     cases.write_rows(tmp_path / "in.bin", scene, rows)
-    r = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=600,
-                       env={"ASAN_OPTIONS": "detect_leaks=0"})
-    print(r.stdout)
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout, r.stderr[-2000:])
+    run_program(exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"))
     orc = pytrack.Track("orc")
     for row, legs in zip(rows, cases.read_results(tmp_path / "out.bin", rows)):
         cases.check(row, cases.oracle_row(orc, scene, row), *legs[0])

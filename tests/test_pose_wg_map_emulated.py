@@ -10,6 +10,7 @@ import pytest
 
 import pose_lds_cases as cases
 import pose_wg_map_cases as wg
+from host_buffers import ptr
 from oracle import pytrack
 from rpg_svo_amd import capi
 
@@ -31,10 +32,6 @@ def shared(oracle):
     return dict(scene=scene, rows=rows, want=want, mixed=mixed, mixed_want=mixed_want, first={})
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def runner(emu, scene, entry="svo_hip_pose_optimize", n_iter=cases.N_ITER):
     cs = capi.camera(scene.cam)
 
@@ -42,8 +39,8 @@ def runner(emu, scene, entry="svo_hip_pose_optimize", n_iter=cases.N_ITER):
         B, ns = len(batch["n"]), batch["ns"]
         T, hp = batch["T0"].copy(), batch["hp"].copy()
         Cov, stats, ran = np.zeros((B, 36)), np.zeros((B, 4)), np.full(B, -1, np.int32)
-        rc = getattr(emu, entry)(C.byref(cs), B, _p(batch["n"]), ns, _p(batch["f"]), _p(batch["level"]), _p(batch["pos"]), _p(hp),
-                                 C.c_double(cases.THRESH), n_iter, _p(T), _p(Cov), _p(stats), _p(ran), None)
+        rc = getattr(emu, entry)(C.byref(cs), B, ptr(batch["n"]), ns, ptr(batch["f"]), ptr(batch["level"]), ptr(batch["pos"]), ptr(hp),
+                                 C.c_double(cases.THRESH), n_iter, ptr(T), ptr(Cov), ptr(stats), ptr(ran), None)
         assert rc == 0, rc
         return T, Cov, stats, ran, hp
     return run

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from helpers import make_batch, marshal_problem, run_oracle
+from host_buffers import ptr
 from rpg_svo_amd import capi, se3, synth
 
 
@@ -32,16 +33,12 @@ def emu_default():
     return build_emulated(())
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)  # (the pointer object keeps the array alive)
-
-
 def run_emulated(emu, b, max_level, min_level, n_iter=30, entry="svo_hip_sparse_align"):
     imgs = np.ascontiguousarray(b.images)
     n, h, w = imgs.shape
     layout = capi.pyr_layout(w, h, b.n_levels)
     store = np.zeros(capi.pyr_store_bytes(layout, n), np.uint8)
-    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), _p(store), 0, n, _p(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
+    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), ptr(store), 0, n, ptr(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
     T_cr, xyz = marshal_problem(b.T_ref_w, b.T_cur_w, b.f, b.pos)
     c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
     ref_slot, cur_slot, nn = c(b.ref_slot, np.int32), c(b.cur_slot, np.int32), c(b.n, np.int32)
@@ -53,8 +50,8 @@ def run_emulated(emu, b, max_level, min_level, n_iter=30, entry="svo_hip_sparse_
     T_out, H = np.zeros((B, 12)), np.zeros((B, 36))
     n_tracked, iters = np.zeros(B, np.int32), np.zeros((B, capi.MAX_LEVELS), np.int32)
     chi2, status = np.zeros(B), np.zeros(B, np.int32)
-    rc = getattr(emu, entry)(C.byref(layout), _p(store), B, _p(ref_slot), _p(cur_slot), _p(nn), ns, _p(px), _p(xyz), _p(valid),
-                                  C.byref(P), _p(T_in), _p(T_out), _p(H), _p(n_tracked), _p(iters), _p(chi2), _p(status), None)
+    rc = getattr(emu, entry)(C.byref(layout), ptr(store), B, ptr(ref_slot), ptr(cur_slot), ptr(nn), ns, ptr(px), ptr(xyz), ptr(valid),
+                                  C.byref(P), ptr(T_in), ptr(T_out), ptr(H), ptr(n_tracked), ptr(iters), ptr(chi2), ptr(status), None)
     assert rc == 0, rc
     return se3.mul(T_out, b.T_ref_w), n_tracked, iters, H, status
 

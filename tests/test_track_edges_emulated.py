@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import track_edge_cases as cases
+from host_buffers import ptr
 from oracle import pytrack
 from rpg_svo_amd import capi
 
@@ -42,16 +43,12 @@ def emu_seeds(request):
     return build_emulated(BUILDS[request.param])
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def _store(emu, images):
     imgs = np.ascontiguousarray(images)
     n, h, w = imgs.shape
     layout = capi.pyr_layout(w, h, cases.N_LEVELS)
     buf = np.zeros(capi.pyr_store_bytes(layout, n), np.uint8)
-    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), _p(buf), 0, n, _p(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
+    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), ptr(buf), 0, n, ptr(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
     return layout, buf
 
 
@@ -89,8 +86,8 @@ def test_find_match_direct(emu, oracle, name, cam_kind):
     ok, ref_obs, sl = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
     A, patches = np.zeros((P, 4)), np.zeros((P, 100), np.uint8)
     ws = _workspace(emu, P)
-    rc = emu.svo_hip_find_match_direct(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), P, _p(cur), _p(pos), _p(c.obs_ptr), C.byref(obs),
-                                       cases.N_LEVELS, 10, _p(px), _p(ok), _p(ref_obs), _p(sl), _p(A), _p(patches), _p(ws), C.c_size_t(ws.size), None)
+    rc = emu.svo_hip_find_match_direct(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), P, ptr(cur), ptr(pos), ptr(c.obs_ptr), C.byref(obs),
+                                       cases.N_LEVELS, 10, ptr(px), ptr(ok), ptr(ref_obs), ptr(sl), ptr(A), ptr(patches), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     worst = cases.verify_matcher(c, ok, px, ref_obs, sl, A, patches)
     print(f"{name} {cam_kind}: max |dA_cur_ref| {worst:.2e}")
@@ -104,8 +101,8 @@ def _epipolar(emu, c, layout, store, align_1d, cap):
     o_ = capi.DepthFilterOptions(0, 0, 0.0, int(align_1d), 10, cap, 1, 1, cases.N_LEVELS, 0.7)
     ok, depth, px, lvl = np.zeros(P, np.int32), np.zeros(P), np.zeros((P, 2)), np.zeros(P, np.int32)
     ws = _workspace(emu, P)
-    rc = emu.svo_hip_find_epipolar_match_direct(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), P, _p(cur), C.byref(ftr), _p(de),
-                                                _p(dmin), _p(dmax), C.byref(o_), _p(ok), _p(depth), _p(px), _p(lvl), _p(ws), C.c_size_t(ws.size), None)
+    rc = emu.svo_hip_find_epipolar_match_direct(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), P, ptr(cur), C.byref(ftr), ptr(de),
+                                                ptr(dmin), ptr(dmax), C.byref(o_), ptr(ok), ptr(depth), ptr(px), ptr(lvl), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     return ok, depth, px, lvl
 
@@ -133,8 +130,8 @@ def _update_seeds(emu, c, layout, store, align_1d, subpix, cap):
     cur = np.full(P, s.cur, np.int32)
     status, xyz, px = np.zeros(P, np.int32), np.zeros((P, 3)), np.zeros((P, 2))
     ws = _workspace(emu, P)
-    rc = emu.svo_hip_update_seeds(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), P, _p(cur), C.byref(ftr), C.byref(sd), C.byref(dopt),
-                                  _p(status), _p(xyz), _p(px), _p(ws), C.c_size_t(ws.size), None)
+    rc = emu.svo_hip_update_seeds(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), P, ptr(cur), C.byref(ftr), C.byref(sd), C.byref(dopt),
+                                  ptr(status), ptr(xyz), ptr(px), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     return status, st["a"], st["b"], st["mu"], st["sigma2"], xyz, px
 

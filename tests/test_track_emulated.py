@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from helpers import FUZZ, camera_models, fuzz_rng
+from host_buffers import ptr
 from oracle import pytrack
 from rpg_svo_amd import capi, synth
 
@@ -25,16 +26,12 @@ def scene(request):
     return synth.make_track_scene(n_kf=4, n_feat=100, cam=camera_models()[request.param], seed=777 + FUZZ)
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)  # (the pointer object keeps the array alive)
-
-
 def _store(emu, scene, n_levels=5):
     imgs = np.ascontiguousarray(scene.images.cpu().numpy())
     n, h, w = imgs.shape
     layout = capi.pyr_layout(w, h, n_levels)
     buf = np.zeros(capi.pyr_store_bytes(layout, n), np.uint8)
-    rc = emu.svo_hip_pyramid_build_tiled(C.byref(layout), _p(buf), 0, n, _p(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None)
+    rc = emu.svo_hip_pyramid_build_tiled(C.byref(layout), ptr(buf), 0, n, ptr(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None)
     assert rc == 0
     return layout, buf
 
@@ -50,10 +47,10 @@ def test_emulated_find_match_direct(emu, oracle, scene):
     slots = np.arange(n_frames, dtype=np.int32)
     frames = capi.Frames(n_frames, 0, slots.ctypes.data, T.ctypes.data)
     P = len(scene.obs)
-    ptr = np.zeros(P + 1, np.int32)
+    obs_ptr = np.zeros(P + 1, np.int32)
     flat = []
     for i, o in enumerate(scene.obs):
-        ptr[i + 1] = ptr[i] + len(o)
+        obs_ptr[i + 1] = obs_ptr[i] + len(o)
         flat.extend(o)
     c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
     o_frame, o_level = c([o[0] for o in flat], np.int32), c([o[3] for o in flat], np.int32)
@@ -68,8 +65,8 @@ def test_emulated_find_match_direct(emu, oracle, scene):
     emu.svo_hip_match_workspace_bytes.restype = C.c_size_t
     ws = np.full(emu.svo_hip_match_workspace_bytes(P) + 256, 0xFF, np.uint8)   # (poisoned: NaN / -1 to whoever reads scratch it did not write)
     cam = capi.camera(scene.cam)
-    rc = emu.svo_hip_find_match_direct(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), P, _p(cur), _p(pos), _p(ptr), C.byref(obs),
-                                       5, 10, _p(px), _p(ok), _p(ref_obs), _p(sl), _p(A), _p(patches), _p(ws), C.c_size_t(ws.size), None)
+    rc = emu.svo_hip_find_match_direct(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), P, ptr(cur), ptr(pos), ptr(obs_ptr), C.byref(obs),
+                                       5, 10, ptr(px), ptr(ok), ptr(ref_obs), ptr(sl), ptr(A), ptr(patches), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     oframes = pytrack.make_frames(pyrs, T)
     opt = pytrack.matcher_options(n_pyr_levels=5)
@@ -78,7 +75,7 @@ def test_emulated_find_match_direct(emu, oracle, scene):
         o = [pytrack.make_feature(*x) for x in scene.obs[i]]
         o_ok, o_pxr, r = orc.find_match_direct(oframes, scene.cam, scene.cur, scene.pt_pos[i], o, scene.px_init[i], opt)
         assert bool(ok[i]) == o_ok, i
-        assert ref_obs[i] - ptr[i] == r["ref_obs"], i
+        assert ref_obs[i] - obs_ptr[i] == r["ref_obs"], i
         if r["A_cur_ref"].any():
             assert sl[i] == r["search_level"]
             assert np.abs(A[i].reshape(2, 2) - r["A_cur_ref"]).max() < 1e-12
@@ -154,8 +151,8 @@ def test_emulated_update_seeds(emu_seeds, oracle, scene, align_1d, subpix):
     ws = np.full(emu.svo_hip_match_workspace_bytes(S) + 256, 0xFF, np.uint8)   # (poisoned: NaN / -1 to whoever reads scratch it did not write)
     cam = capi.camera(scene.cam)
     state0 = [x.copy() for x in (a, b, mu, zr, s2, bid)]
-    rc = emu.svo_hip_update_seeds(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), S, _p(cur), C.byref(ftr), C.byref(sd),
-                                  C.byref(dopt), _p(status), _p(xyz), _p(px), _p(ws), C.c_size_t(ws.size), None)
+    rc = emu.svo_hip_update_seeds(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), S, ptr(cur), C.byref(ftr), C.byref(sd),
+                                  C.byref(dopt), ptr(status), ptr(xyz), ptr(px), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     # The same seeds keyframe by keyframe, as a seed list holds them: a wave of seed_prepare_kernel then finds a handful of
     # RUNS of equal (reference, current) pairs whose first seed files the pair's poses for seed_finish (in the list order
@@ -169,8 +166,8 @@ def test_emulated_update_seeds(emu_seeds, oracle, scene, align_1d, subpix):
         psd = capi.Seeds(*[x.ctypes.data for x in ps])
         st2, xyz2, px2 = np.zeros(S, np.int32), np.zeros((S, 3)), np.zeros((S, 2))
         ws2 = np.full(ws.size, 0xFF, np.uint8)
-        rc = emu.svo_hip_update_seeds(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), S, _p(cur), C.byref(pftr), C.byref(psd),
-                                      C.byref(dopt), _p(st2), _p(xyz2), _p(px2), _p(ws2), C.c_size_t(ws_bytes), None)
+        rc = emu.svo_hip_update_seeds(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), S, ptr(cur), C.byref(pftr), C.byref(psd),
+                                      C.byref(dopt), ptr(st2), ptr(xyz2), ptr(px2), ptr(ws2), C.c_size_t(ws_bytes), None)
         assert rc == 0, rc
         assert np.array_equal(st2, status[order]) and np.array_equal(px2, px[order])
         conv = status[order] == pytrack.SEED_CONVERGED
@@ -233,8 +230,8 @@ def test_emulated_update_seeds_on_the_resident_store(emu_seeds, scene):
     ftr0, sd0 = structs(f0, s0)
     cur = np.full(S, scene.cur, np.int32)
     st0, xyz0, px0 = np.zeros(S, np.int32), np.zeros((S, 3)), np.zeros((S, 2))
-    assert emu.svo_hip_update_seeds(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), S, _p(cur), C.byref(ftr0), C.byref(sd0),
-                                    C.byref(dopt), _p(st0), _p(xyz0), _p(px0), _p(ws), C.c_size_t(ws.size), None) == 0
+    assert emu.svo_hip_update_seeds(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), S, ptr(cur), C.byref(ftr0), C.byref(sd0),
+                                    C.byref(dopt), ptr(st0), ptr(xyz0), ptr(px0), ptr(ws), C.c_size_t(ws.size), None) == 0
     # resident store of 3 S slots, patched in two instalments
     cap = 3 * S
     slot_of = rng.permutation(cap)[:S].astype(np.int32)
@@ -249,8 +246,8 @@ def test_emulated_update_seeds_on_the_resident_store(emu_seeds, scene):
         assert emu.svo_hip_seed_store_patch(C.byref(patch), C.byref(ftrS), C.byref(sdS), None) == 0
     ws[:] = 0xFF
     st1, xyz1, px1, state = np.zeros(S, np.int32), np.zeros((S, 3)), np.zeros((S, 2)), np.zeros((4, S), np.float32)
-    assert emu.svo_hip_update_seeds_resident(C.byref(layout), _p(store), C.byref(cam), C.byref(frames), int(scene.cur), S, _p(slot_of), C.byref(ftrS),
-                                             C.byref(sdS), C.byref(dopt), _p(st1), _p(xyz1), _p(px1), _p(state), _p(ws), C.c_size_t(ws.size), None) == 0
+    assert emu.svo_hip_update_seeds_resident(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames), int(scene.cur), S, ptr(slot_of), C.byref(ftrS),
+                                             C.byref(sdS), C.byref(dopt), ptr(st1), ptr(xyz1), ptr(px1), ptr(state), ptr(ws), C.c_size_t(ws.size), None) == 0
     assert np.array_equal(st0, st1) and np.array_equal(px0, px1)
     conv = st0 == pytrack.SEED_CONVERGED
     assert np.array_equal(xyz0[conv], xyz1[conv]) and conv.sum() > 2
@@ -281,13 +278,13 @@ def test_emulated_update_seeds_on_the_resident_store(emu_seeds, scene):
     frames_p = capi.Frames(n_frames, 0, slots_f.ctypes.data, T_poisoned.ctypes.data)
     ws[:] = 0xFF
     st2, xyz2, px2, state2 = np.zeros(S, np.int32), np.zeros((S, 3)), np.zeros((S, 2)), np.zeros((4, S), np.float32)
-    assert emu.svo_hip_update_seeds_resident_pose(C.byref(layout), _p(store), C.byref(cam), C.byref(frames_p), int(scene.cur), _p(T_cur), S,
-                                                  _p(slot_of), C.byref(ftrS2), C.byref(sdS2), C.byref(dopt), _p(st2), _p(xyz2), _p(px2),
-                                                  _p(state2), _p(ws), C.c_size_t(ws.size), None) == 0
+    assert emu.svo_hip_update_seeds_resident_pose(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames_p), int(scene.cur), ptr(T_cur), S,
+                                                  ptr(slot_of), C.byref(ftrS2), C.byref(sdS2), C.byref(dopt), ptr(st2), ptr(xyz2), ptr(px2),
+                                                  ptr(state2), ptr(ws), C.c_size_t(ws.size), None) == 0
     assert np.array_equal(st2, st1) and np.array_equal(px2, px1) and np.array_equal(xyz2[conv], xyz1[conv])
     assert np.array_equal(state2[:, touched].view(np.int32), state[:, touched].view(np.int32))
     for k in (0, 1, 2, 4):
         assert np.array_equal(sS2[k].view(np.int32), sS[k].view(np.int32))
-    assert emu.svo_hip_update_seeds_resident_pose(C.byref(layout), _p(store), C.byref(cam), C.byref(frames_p), int(scene.cur), None, S,
-                                                  _p(slot_of), C.byref(ftrS2), C.byref(sdS2), C.byref(dopt), _p(st2), _p(xyz2), _p(px2),
-                                                  _p(state2), _p(ws), C.c_size_t(ws.size), None) == -1  # (EINVAL: no pose)
+    assert emu.svo_hip_update_seeds_resident_pose(C.byref(layout), ptr(store), C.byref(cam), C.byref(frames_p), int(scene.cur), None, S,
+                                                  ptr(slot_of), C.byref(ftrS2), C.byref(sdS2), C.byref(dopt), ptr(st2), ptr(xyz2), ptr(px2),
+                                                  ptr(state2), ptr(ws), C.c_size_t(ws.size), None) == -1  # (EINVAL: no pose)

@@ -23,7 +23,8 @@ import torch
 
 import frame_close_cases as cases
 import frame_close_checker as chk
-from first_map_cases import compare_device, relative_difference, same_bits
+from first_map_cases import compare_device
+from host_buffers import relative_difference, same_bits
 from test_bootstrap_to_tracking_gpu import bootstrap
 
 pytestmark = pytest.mark.gpu
