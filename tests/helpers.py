@@ -202,8 +202,8 @@ def oracle_reproject_map(mp, cam, first_cell=0, max_cells=1 << 30):
 
 
 # SVO_TEST_FUZZ=<k> (default 0: the suites as committed) moves the track scene's trajectory, features and depth errors and
-# every random draw of the tracking suites (tests/test_tracking_gpu.py, test_track_emulated.py, test_optimizers_emulated.py)
-# to other seeds: scripts/fuzz_tracking.sh runs them over a range of k -- the bit-exact asserts on scenes nobody has looked at.
+# every random draw of the tracking suites (tests/tracking_cases.py: test_tracking_gpu.py, test_track_emulated.py,
+# test_optimizers_emulated.py) to other seeds: scripts/fuzz_tracking.sh runs them over a range of k -- the bit-exact asserts on scenes nobody has looked at.
 FUZZ = int(os.environ.get("SVO_TEST_FUZZ", "0"))
 
 

@@ -10,11 +10,12 @@ observations into LDS and walks them in trips of 64.  Sixteen frames per row len
   * the places left of the sixteen: ~20 % of the row dead at random;
   * every 15th point grossly wrong, as tests/test_tracking_gpu.py::test_pose_optimize has them, so that pruning fires.
 
-check() compares one row's results with the oracle under the requirements of that test (and nothing wider)."""
+check() compares one row's results with the oracle under the requirements of that test (tracking_cases.check_pose)."""
 import numpy as np
 
 from helpers import FUZZ, camera_models, fuzz_rng
 from rpg_svo_amd import se3, synth
+from tracking_cases import check_pose, check_pose_median
 
 ROWS = (7, 64, 65, 200, 250, 256)
 COUNTS = (0, 1, 5, 20, 63, 64, 65, 127, 128, 129, 191, 192, 193)
@@ -106,35 +107,13 @@ def moved_and_pruned(row, want):
 
 
 def check(row, want, T, Cov, stats, ran, hp_out):
-    """the requirements of tests/test_tracking_gpu.py::test_pose_optimize on every frame that ran, none skipped on the
-    committed scene; flags beyond n untouched"""
-    n, hp, T0, devs = row["n"], row["hp"], row["T0"], []
-    for b in range(B):
-        o, tag = want[b], (row["ns"], b, row["what"][b])
-        assert ran[b] == o["ran"], tag
-        assert np.array_equal(hp_out[b, n[b]:], hp[b, n[b]:]), tag
-        if not o["ran"]:
-            assert np.array_equal(T[b], T0[b]) and np.array_equal(hp_out[b], hp[b]), tag
-            continue
-        live = int(hp[b, :n[b]].sum())
-        if FUZZ and live < 6:  # (rank-deficient or nearly: see tests/test_tracking_gpu.py::test_pose_optimize)
-            assert np.isfinite(T[b]).all() == np.isfinite(o["T_f_w"]).all(), tag
-            continue
-        dev_b = se3.log_norm(T[b][None], o["T_f_w"][None])[0]
-        if live >= 20:
-            devs.append(dev_b)
-        assert dev_b < (2e-8 if live >= 20 else 1e-7), (tag, dev_b)
-        assert np.array_equal(hp_out[b, :n[b]], o["has_point"]), tag
-        assert stats[b, 3] == o["num_obs"], tag
-        assert np.allclose(stats[b, :3], [o["estimated_scale"], o["error_init"], o["error_final"]],
-                           rtol=1e-9 if dev_b < 1e-11 else 1e-6, atol=1e-12), (tag, dev_b)
-        # (Cov is the inverse of the 6x6 normal matrix, whose rank is at most twice the number of live observations: below three
-        #  of them it is singular and its "inverse" rounding noise of magnitude 1e13 on every side -- the oracle's, the ordered
-        #  kernel's that finishes such a frame.  The table has frames of one live observation among n >= 40 slots.)
-        if n[b] >= 40 and live >= 3:
-            assert np.allclose(Cov[b].reshape(6, 6), o["Cov"], rtol=1e-6, atol=1e-14), tag
+    """tracking_cases.check_pose (the requirements of tests/test_tracking_gpu.py::test_pose_optimize) on every frame that ran,
+    none skipped on the committed scene, with the tight bound on scale and errors wherever the pose agrees to 1e-11; flags
+    beyond n untouched; the median where a row has frames of 20 or more live observations"""
+    devs = check_pose(row["n"], row["hp"], row["T0"], want, T, Cov, stats, ran, hp_out, beyond_n=True, tight_stats_live=0,
+                      what=[(row["ns"], w) for w in row["what"]])
     if devs:
-        assert np.median(devs) < 1e-12, devs
+        check_pose_median(devs)
     return devs
 
 

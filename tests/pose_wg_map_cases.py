@@ -15,8 +15,9 @@ A batch is a dict of per-frame arrays: ns, n [B], f [B,ns,3], level [B,ns], pos 
 import numpy as np
 
 import pose_lds_cases as cases
-from helpers import FUZZ, fuzz_rng
+from helpers import fuzz_rng
 from rpg_svo_amd import se3, synth
+from tracking_cases import check_pose
 
 ROWS = (8, 200, 256)
 BATCHES = (1, 2, 3, 4, 5, 9)
@@ -117,28 +118,9 @@ def check_mixed_classes(batch, want, ran_deferred):
 
 
 def check_frames(batch, want, T, Cov, stats, ran, hp_out):
-    """the requirements of pose_lds_cases.check (tests/test_tracking_gpu.py::test_pose_optimize) frame by frame, for a batch
-    whose frames have their own observations"""
-    n, hp = batch["n"], batch["hp"]
-    for b, o in enumerate(want):
-        tag = (b, batch["what"][b])
-        assert ran[b] == o["ran"], tag
-        assert np.array_equal(hp_out[b, n[b]:], hp[b, n[b]:]), tag
-        if not o["ran"]:
-            assert np.array_equal(T[b], batch["T0"][b]) and np.array_equal(hp_out[b], hp[b]), tag
-            continue
-        live = int(hp[b, :n[b]].sum())
-        if FUZZ and live < 6:
-            assert np.isfinite(T[b]).all() == np.isfinite(o["T_f_w"]).all(), tag
-            continue
-        dev_b = se3.log_norm(T[b][None], o["T_f_w"][None])[0]
-        assert dev_b < (2e-8 if live >= 20 else 1e-7), (tag, dev_b)
-        assert np.array_equal(hp_out[b, :n[b]], o["has_point"]), tag
-        assert stats[b, 3] == o["num_obs"], tag
-        assert np.allclose(stats[b, :3], [o["estimated_scale"], o["error_init"], o["error_final"]],
-                           rtol=1e-9 if dev_b < 1e-11 else 1e-6, atol=1e-12), (tag, dev_b)
-        if n[b] >= 40 and live >= 3:
-            assert np.allclose(Cov[b].reshape(6, 6), o["Cov"], rtol=1e-6, atol=1e-14), tag
+    """the requirements of pose_lds_cases.check (tracking_cases.check_pose) frame by frame, for a batch whose frames have their
+    own observations"""
+    check_pose(batch["n"], batch["hp"], batch["T0"], want, T, Cov, stats, ran, hp_out, beyond_n=True, tight_stats_live=0, what=batch["what"])
 
 
 def width_frames(row):

@@ -93,9 +93,17 @@ def test_sparse_align_on_any_shape_at_reference_width(emu_reference_width, oracl
 @pytest.mark.parametrize("kind", ["pinhole", "atan"])
 def test_matcher_and_depth_filter_on_an_odd_image_size(emu, oracle, kind):
     """find_match_direct and update_seeds (tests/test_track_emulated.py) on 438 x 410 images: 27.4 x 51.25 tiles of the store"""
-    import test_track_emulated as tte
+    import tracking_cases as tc
+    import tracking_emulated as te
     cam = synth.Camera(438, 410, 260.0, 260.0, 219.0, 205.0) if kind == "pinhole" else \
         synth.Camera.atan(438, 410, 0.509326, 0.796651, 0.45905, 0.510056, 0.9320)
     scene = synth.make_track_scene(n_kf=4, n_feat=100, cam=cam)
-    tte.test_emulated_find_match_direct(emu, oracle, scene)
-    tte.test_emulated_update_seeds(emu, oracle, scene, 0, 1)
+    c = tc.of_scene(scene, "odd size")
+    tc.verify_matcher(c, *te.find_match_direct(emu, c))
+    n_ok, n_edge = tc.matcher_coverage(c)
+    assert n_ok > 200 and n_edge > 20
+    first = te.update_seeds(emu, c, 0, 1, 1000)
+    order = tc.seed_order(c)
+    tc.verify_seed_order(order, first, te.update_seeds(emu, c, 0, 1, 1000, order))
+    tc.verify_seeds(c, 0, 1, 1000, *first)
+    tc.seed_coverage(c)

@@ -3,7 +3,7 @@ tests/track_edge_cases.py -- those of tests/test_track_edges_emulated.py, here w
 hand-overs through LDS inside a wave and fused multiply-adds: feature and search levels 0 to 4 (L), the gather path of the
 warp (Z), borders with the clamped box, warp_sample<true> and the all-zero patch (B), lines from under two pixels to beyond
 the cap through every bucket of the scan, the box per half group on the ATAN camera, and the resident entry (E).  On all
-of CAMERA_KINDS, against both checkers, by the rules of tests/test_tracking_gpu.py unchanged (track_edge_cases.verify_*).
+of CAMERA_KINDS, against both checkers, by the rules of tests/tracking_cases.py (verify_*), through tests/tracking_device.py.
 Every test prints its class counts and its largest deviations.
 
 Measured on an MI355X (93 tests, 21 s): every verdict, observation, search level, patch and refined pixel identical in all
@@ -14,43 +14,16 @@ rule's 4 eps32 (sigma2 + mu^2)) and below 8e-6 elsewhere, a / b 5.5e-6 (L10, rad
 1e-9 rule on px_cur needed no change on lines of up to 1000 additions."""
 import numpy as np
 import pytest
-import torch
 
 import track_edge_cases as cases
+import tracking_cases as tc
+import tracking_device as td
 from helpers import CAMERA_KINDS
-from oracle import pytrack
-from rpg_svo_amd import tracking
-from rpg_svo_amd.pyramid import PyramidStore
 
 pytestmark = pytest.mark.gpu
 
 NAMES = tuple(n for g in cases.COVERAGE for n in cases.COVERAGE[g][0])
 GROUP_OF = {n: g for g in cases.COVERAGE for n in cases.COVERAGE[g][0]}
-
-
-def dev(a, dt):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device="cuda:0")
-
-
-def _store(c, T):
-    s = c.scene
-    n = s.images.shape[0]
-    store = PyramidStore(s.cam.width, s.cam.height, cases.N_LEVELS, n, device="cuda:0")
-    store.load_images(torch.from_numpy(s.images).to("cuda:0"))
-    return store, tracking.FrameTable(torch.arange(n, dtype=torch.int32, device="cuda:0"), dev(T, torch.float64))
-
-
-def _fs(cols, idx=None):
-    sel = (lambda a: a) if idx is None else (lambda a: a[idx])
-    return tracking.FeatureSet(frame=dev(sel(cols["frame"]), torch.int32), level=dev(sel(cols["level"]), torch.int32), px=dev(sel(cols["px"]), torch.float64),
-                               f=dev(sel(cols["f"]), torch.float64), type=dev(sel(cols["type"]), torch.uint8), grad=dev(sel(cols["grad"]), torch.float64))
-
-
-def _ss(cols, idx=None):
-    sel = (lambda a: a) if idx is None else (lambda a: a[idx])
-    return tracking.SeedSet(a=dev(sel(cols["a"]), torch.float32), b=dev(sel(cols["b"]), torch.float32), mu=dev(sel(cols["mu"]), torch.float32),
-                            z_range=dev(sel(cols["z_range"]), torch.float32), sigma2=dev(sel(cols["sigma2"]), torch.float32),
-                            batch_id=dev(sel(cols["batch_id"]), torch.int32))
 
 
 def _case(name, cam_kind):
@@ -63,14 +36,7 @@ def _case(name, cam_kind):
 @pytest.mark.parametrize("name", NAMES)
 def test_find_match_direct(gpu_device, checker, name, cam_kind):
     c = _case(name, cam_kind)
-    s, P = c.scene, c.P
-    store, frames = _store(c, c.T_match)
-    m = tracking.Matcher(align_max_iter=10, n_pyr_levels=cases.N_LEVELS)
-    res = m.find_match_direct(store, s.cam, frames, torch.full((P,), s.cur, dtype=torch.int32, device="cuda:0"), dev(s.pt_pos, torch.float64),
-                              dev(c.obs_ptr, torch.int32), _fs(c.obs_cols), dev(s.px_init, torch.float64))
-    torch.cuda.synchronize()
-    worst = cases.verify_matcher(c, res.ok.cpu().numpy(), res.px_cur.cpu().numpy(), res.ref_obs.cpu().numpy(), res.search_level.cpu().numpy(),
-                                 res.A_cur_ref.cpu().numpy(), res.patch_with_border.cpu().numpy(), which=checker)
+    worst = tc.verify_matcher(c, *td.find_match_direct(c), which=checker)
     print(f"{name} {cam_kind} [{checker}]: max |dA_cur_ref| {worst:.2e}")
 
 
@@ -78,69 +44,28 @@ def test_find_match_direct(gpu_device, checker, name, cam_kind):
 @pytest.mark.parametrize("name", NAMES)
 def test_find_epipolar_match_direct(gpu_device, checker, name, cam_kind):
     c = _case(name, cam_kind)
-    s, P = c.scene, c.P
-    store, frames = _store(c, s.T_f_w)
-    fs, cur = _fs(c.ftr_cols), torch.full((P,), s.cur, dtype=torch.int32, device="cuda:0")
-    de, dmin, dmax = dev(c.d_est, torch.float64), dev(c.d_min, torch.float64), dev(c.d_max, torch.float64)
     for align_1d, cap in [(0, 1000), (1, 1000)] + ([(0, c.cap)] if c.cap else []):
-        out = tracking.find_epipolar_match_direct(store, s.cam, frames, cur, fs, de, dmin, dmax, n_pyr_levels=cases.N_LEVELS, align_1d=bool(align_1d),
-                                                  max_epi_search_steps=cap)
-        torch.cuda.synchronize()
-        wpx, wd = cases.verify_epipolar(c, align_1d, cap, *[t.cpu().numpy() for t in out], which=checker)
+        wpx, wd = tc.verify_epipolar(c, align_1d, cap, *td.find_epipolar(c, c.epi, align_1d, cap), which=checker)
         print(f"{name} {cam_kind} [{checker}] align_1d={align_1d} cap={cap}: max |dpx_cur| {wpx:.2e}, max relative depth difference {wd:.2e}")
-
-
-def _update(c, store, frames, align_1d, subpix, cap):
-    s, P = c.scene, c.P
-    fs, ss = _fs(c.ftr_cols), _ss(c.seed_cols)
-    df = tracking.DepthFilter(n_pyr_levels=cases.N_LEVELS, align_1d=bool(align_1d), subpix_refinement=bool(subpix), max_epi_search_steps=cap)
-    status, xyz, px = df.update_seeds(store, s.cam, frames, torch.full((P,), s.cur, dtype=torch.int32, device="cuda:0"), fs, ss, batch_counter=5)
-    torch.cuda.synchronize()
-    return df, ss, (status, xyz, px)
 
 
 @pytest.mark.parametrize("cam_kind", CAMERA_KINDS)
 @pytest.mark.parametrize("name", NAMES)
 def test_update_seeds(gpu_device, checker, name, cam_kind):
     c = _case(name, cam_kind)
-    store, frames = _store(c, c.scene.T_f_w)
     for align_1d, subpix, cap in [(0, 1, 1000)] + ([(0, 0, 1000), (0, 1, c.cap)] if c.cap else []):
-        _, ss, (status, xyz, px) = _update(c, store, frames, align_1d, subpix, cap)
-        w = cases.verify_seeds(c, align_1d, subpix, cap, status.cpu().numpy(), ss.a.cpu().numpy(), ss.b.cpu().numpy(), ss.mu.cpu().numpy(),
-                               ss.sigma2.cpu().numpy(), xyz.cpu().numpy(), px.cpu().numpy(), which=checker, device=True)
-        print(f"{name} {cam_kind} [{checker}] align_1d={align_1d} subpix={subpix} cap={cap}: max deviations " + ", ".join(f"{k} {v:.2e}" for k, v in w.items()))
+        w = tc.verify_seeds(c, align_1d, subpix, cap, *td.update_seeds(c, align_1d, subpix, cap), which=checker, device=True)
+        print(f"{name} {cam_kind} [{checker}] align_1d={align_1d} subpix={subpix} cap={cap}: max deviations {tc.format_deviations(w)}")
 
 
 @pytest.mark.parametrize("cam_kind", CAMERA_KINDS)
 def test_long_lines_on_the_resident_store(gpu_device, oracle, cam_kind):
-    """Case E through svo_hip_update_seeds_resident: the bits of the flat entry, as tests/test_tracking_gpu.py::
-    test_update_seeds_on_the_resident_store demands -- statuses, points, px_cur, the state in the store and in the dense
-    read-back; slots nobody named untouched."""
+    """Case E through svo_hip_update_seeds_resident: the bits of the flat entry (tracking_cases.verify_resident) -- statuses,
+    points, px_cur, the state in the store and in the dense read-back; slots nobody named untouched."""
     c = _case("E", cam_kind)
-    s, P = c.scene, c.P
-    store, frames = _store(c, s.T_f_w)
-    df, ss, (st0, xyz0, px0) = _update(c, store, frames, 0, 1, 1000)
-    cap = 3 * P
-    slots = np.random.default_rng(5).permutation(cap)[:P].astype(np.int32)
-    z = lambda n, dt: torch.full((n,) if isinstance(n, int) else n, 77, dtype=dt, device="cuda:0")
-    sf = tracking.FeatureSet(frame=z(cap, torch.int32), level=z(cap, torch.int32), px=z((cap, 2), torch.float64), f=z((cap, 3), torch.float64),
-                             type=z(cap, torch.uint8), grad=z((cap, 2), torch.float64))
-    sst = tracking.SeedSet(a=z(cap, torch.float32), b=z(cap, torch.float32), mu=z(cap, torch.float32), z_range=z(cap, torch.float32),
-                           sigma2=z(cap, torch.float32), batch_id=z(cap, torch.int32))
-    for part in (np.arange(P // 2), np.arange(P // 2, P)):
-        tracking.DepthFilter.seed_store_patch(dev(slots[part], torch.int32), _fs(c.ftr_cols, part), _ss(c.seed_cols, part), sf, sst)
-    st1, xyz1, px1, state = df.update_seeds_resident(store, s.cam, frames, s.cur, dev(slots, torch.int32), sf, sst, batch_counter=5)
-    torch.cuda.synchronize()
-    assert torch.equal(st0, st1) and torch.equal(px0, px1)
-    conv = st0 == pytrack.SEED_CONVERGED
-    assert torch.equal(xyz0[conv], xyz1[conv])
-    sl = torch.as_tensor(slots.astype(np.int64), device="cuda:0")
-    touched = torch.isin(st0, torch.tensor([pytrack.SEED_NO_MATCH, pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED, pytrack.SEED_NAN], device="cuda:0"))
-    for name, k in (("a", 0), ("b", 1), ("mu", 2), ("sigma2", 3)):
-        flat, resident = getattr(ss, name), getattr(sst, name)[sl]
-        assert torch.equal(flat.view(torch.int32), resident.view(torch.int32)), name
-        assert torch.equal(state[k][touched].view(torch.int32), flat[touched].view(torch.int32)), name
-    free = torch.ones(cap, dtype=torch.bool, device="cuda:0")
-    free[sl] = False
-    assert (sst.mu[free] == 77).all() and (sf.level[free] == 77).all() and (sst.batch_id[free] == 77).all()
-    print(f"E {cam_kind} resident: {int(touched.sum())} seeds updated, {int(conv.sum())} converged, identical to the flat entry")
+    P = c.P
+    st0, a, b, mu, s2, xyz0, px0 = td.update_seeds(c, 0, 1, 1000)
+    slots = np.random.default_rng(5).permutation(3 * P)[:P].astype(np.int32)
+    resident = td.update_seeds_resident(c, slots, (np.arange(P // 2), np.arange(P // 2, P)))
+    touched, conv = tc.verify_resident(slots, 3 * P, (st0, xyz0, px0, dict(a=a, b=b, mu=mu, sigma2=s2)), resident)
+    print(f"E {cam_kind} resident: {touched} seeds updated, {conv} converged, identical to the flat entry")

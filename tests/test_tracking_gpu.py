@@ -1,32 +1,25 @@
 """GPU parity of the kernels behind rows a8-a13 (matcher / feature alignment / pose optimizer /
 point optimizer / depth filter) against the oracle, through the C ABI.
 
-Tolerances.  The float pipelines (feature alignment, affine warp) and every integer result
-(patch bytes, ZMSSD argmin, statuses, pruning flags) are required to be IDENTICAL to the
-oracle's: the kernels keep the reference's evaluation order and run with contraction off.
-f64 geometry may differ in the last bits (GPU libm sin/cos/acos/atan, quaternion selects), so
-poses / depths / covariances carry explicit tolerances stated at each assert.
+The cases, the rules and their tolerances are those of tests/tracking_cases.py, which the host-emulated tests share
+(tests/test_track_emulated.py, test_optimizers_emulated.py, test_entries_emulated.py); tests/tracking_device.py makes the
+calls.  The float pipelines (feature alignment, affine warp) and every integer result (patch bytes, ZMSSD argmin, statuses,
+pruning flags) are required to be IDENTICAL to the oracle's; f64 geometry carries the tolerance stated at its assert there.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
 
-from helpers import CAMERA_KINDS, FUZZ, camera_models, fuzz_rng, obs_csr, scene_store
+import tracking_cases as tc
+import tracking_device as td
+from helpers import CAMERA_KINDS, camera_models, fuzz_rng
 from oracle import pytrack
-from rpg_svo_amd import capi, se3, synth, tracking
+from rpg_svo_amd import capi, se3, tracking
+from tracking_device import dev
 
 pytestmark = pytest.mark.gpu
-
-# DepthFilter::updateSeed's a and b, device against CPU.  (e - f) / (f - e / f) cancels: a last-bit difference of an input
-# comes out amplified.  Measured on 200 000 seeds with IDENTICAL float inputs (scripts/update_seed_parity.py on the GPU box,
-# profiles/r04_update_seed_parity.json, the same against the C port and the reference's own translation unit): 99.98 % of
-# the seeds come back with identical bits in all four fields (the rest: an exp that rounds the other way); largest
-# relative deviation a 2.07e-5, b 2.04e-5, mu 1.7e-7, sigma2 1.7e-4 (a difference of two nearly equal products).
-AB_RTOL_SAME_INPUTS = 1e-4   # 5 x the measured maximum
-# In updateSeeds the inputs themselves (x = 1 / z, tau^2) come out of f64 geometry through acos / atan / sin, which can differ
-# in the last bits between glibc and the GPU's libm before x is rounded to float.  Measured on the GPU box (this test prints
-# it): 0.0 -- identical a and b -- on all 255 compared seeds of each of the six runs (3 option sets x 2 checkers).
-AB_RTOL = 1e-4
 
 
 @pytest.fixture(scope="module")
@@ -37,748 +30,204 @@ def orc(oracle, checker):
 
 
 @pytest.fixture(scope="module", params=CAMERA_KINDS)
-def scene(request):
-    """the same scene seen through each vikit camera model (undistorted pinhole, the reference's
-    camera_pinhole.yaml with radial-tangential distortion, its camera_atan.yaml)"""
-    return synth.make_track_scene(n_kf=4, n_feat=100, cam=camera_models()[request.param], seed=777 + FUZZ)
+def case(request):
+    """the committed scene seen through each vikit camera model"""
+    return tc.committed(request.param)
 
 
-@pytest.fixture(scope="module")
-def pyrs(scene, orc):
-    return [orc.create_img_pyramid(im, 5) for im in scene.images.cpu().numpy()]
+def _counted(store, tr, M, h_inv=True):
+    """svo_hip_align_batch_counted on the first M trials -> px, ok, h_inv, evaluations"""
+    px = dev(tr["px0"][:M], torch.float64)
+    ok = torch.zeros(M, dtype=torch.int32, device="cuda:0")
+    h = torch.zeros(M, dtype=torch.float64, device="cuda:0")
+    ev = torch.zeros(M, dtype=torch.int32, device="cuda:0")
+    keep = (dev(tr["slot"][:M], torch.int32), dev(tr["level"][:M], torch.int32), dev(tr["pwb"][:M], torch.uint8), dev(tr["dirs"][:M], torch.float32),
+            dev(tr["use_1d"][:M], torch.uint8))
+    capi.check(capi.load().svo_hip_align_batch_counted(C.byref(store.layout), store.ptr, M, keep[0].data_ptr(), keep[1].data_ptr(),
+                                                       keep[2].data_ptr(), keep[3].data_ptr(), keep[4].data_ptr(), 10, px.data_ptr(), ok.data_ptr(),
+                                                       h.data_ptr() if h_inv else None, ev.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return td.host((px, ok, h, ev))
 
 
-def dev(a, dt, device="cuda:0"):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=device)
+def test_align_batch_bit_exact(gpu_device, orc, case):
+    _, pyrs, _, _ = case.checker(orc.which)
+    store, _ = td.store_and_frames(case, case.T_f_w)
+    M, n_iter = 3000, 10
+    tr = tc.align_trials(pyrs, fuzz_rng(3), M, 2.5)
+    px, ok, h_inv = td.align_batch(store, tr, n_iter)
+    assert tc.check_alignment(orc, pyrs, tr, n_iter, ok, px, h_inv) > M // 4
 
 
-def test_align_batch_bit_exact(gpu_device, orc, scene, pyrs):
-    store, _ = scene_store(scene)
-    rng = fuzz_rng(3)
-    M = 3000
-    imgs = scene.images.cpu().numpy()
-    slot = rng.integers(0, imgs.shape[0], size=M).astype(np.int32)
-    level = rng.integers(0, 3, size=M).astype(np.int32)
-    pwb = np.zeros((M, 100), np.uint8)
-    px0 = np.zeros((M, 2))
-    dirs = rng.normal(size=(M, 2)).astype(np.float32)
-    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
-    use_1d = (rng.uniform(size=M) < 0.3).astype(np.uint8)
-    for t in range(M):
-        img = pyrs[slot[t]][level[t]]
-        h, w = img.shape
-        u, v = rng.integers(8, w - 8), rng.integers(8, h - 8)
-        src = pyrs[(slot[t] + (t % 2)) % imgs.shape[0]][level[t]]      # same or neighbouring frame
-        pwb[t] = src[v - 5:v + 5, u - 5:u + 5].ravel()
-        px0[t] = [u + rng.uniform(-2.5, 2.5), v + rng.uniform(-2.5, 2.5)]
-        if t % 37 == 0:
-            px0[t] = [3.0 + rng.uniform(0, 2), v]                       # leaves the image
-        if t % 41 == 0:
-            pwb[t] = 77                                                 # singular H -> NaN
-    n_iter = 10
-    px = dev(px0, torch.float64)
-    ok, h_inv = tracking.align_batch(store, dev(slot, torch.int32), dev(level, torch.int32), dev(pwb, torch.uint8), px,
-                                     n_iter, dir=dev(dirs, torch.float32), use_1d=dev(use_1d, torch.uint8))
-    torch.cuda.synchronize()
-    ok, px, h_inv = ok.cpu().numpy(), px.cpu().numpy(), h_inv.cpu().numpy()
-    n_conv = 0
-    for t in range(M):
-        img = pyrs[slot[t]][level[t]]
-        patch = pwb[t].reshape(10, 10)[1:9, 1:9].ravel()
-        if use_1d[t]:
-            o, p, hi = orc.align1d(img, dirs[t], pwb[t], patch, n_iter, px0[t])
-            assert hi == h_inv[t] or (np.isnan(hi) and np.isnan(h_inv[t])) or (np.isinf(hi) and np.isinf(h_inv[t])), t
-        else:
-            o, p = orc.align2d(img, pwb[t], patch, n_iter, px0[t])
-        assert bool(ok[t]) == o, t
-        assert np.array_equal(p, px[t], equal_nan=True), (t, p, px[t])
-        n_conv += o
-    assert n_conv > M // 4
-
-
-def test_wave_per_trial_alignment_is_the_lane_kernel_bit_for_bit(gpu_device, scene, pyrs):
+def test_wave_per_trial_alignment_is_the_lane_kernel_bit_for_bit(gpu_device, orc, case):
     """Batches of up to 8192 trials are aligned by one wave per trial (csrc/align_wave.h: a camera frame's trials), larger
     ones by one lane per trial (align_lanes.h).  The same 3000 trials alone (wave kernel) and as the head of a batch of
     9000 (lane kernel): verdicts, refined pixels, h_inv and evaluation counts identical in every bit.  Each kernel is
     pinned to the reference on its own: test_align_batch_bit_exact (3000 trials: the wave kernel), the full-size and
     phased tests (the lane kernel)."""
-    import ctypes as C
-    store, _ = scene_store(scene)
-    rng = fuzz_rng(23)
+    store, _ = td.store_and_frames(case, case.T_f_w)
     M0, M1 = 3000, 9000
-    imgs = scene.images.cpu().numpy()
-    slot = rng.integers(0, imgs.shape[0], size=M1).astype(np.int32)
-    level = rng.integers(0, 3, size=M1).astype(np.int32)
-    pwb = np.zeros((M1, 100), np.uint8)
-    px0 = np.zeros((M1, 2))
-    dirs = rng.normal(size=(M1, 2)).astype(np.float32)
-    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
-    use_1d = (rng.uniform(size=M1) < 0.3).astype(np.uint8)
-    for t in range(M1):
-        img = pyrs[slot[t]][level[t]]
-        h, w = img.shape
-        u, v = rng.integers(8, w - 8), rng.integers(8, h - 8)
-        src = pyrs[(slot[t] + (t % 2)) % imgs.shape[0]][level[t]]
-        pwb[t] = src[v - 5:v + 5, u - 5:u + 5].ravel()
-        px0[t] = [u + rng.uniform(-4.0, 4.0), v + rng.uniform(-4.0, 4.0)]
-        if t % 37 == 0:
-            px0[t] = [3.0 + rng.uniform(0, 2), v]                       # leaves the image
-        if t % 41 == 0:
-            pwb[t] = 77                                                 # singular H -> NaN
-    lib = capi.load()
-
-    def run(M):
-        px = dev(px0[:M], torch.float64)
-        ok = torch.zeros(M, dtype=torch.int32, device="cuda:0")
-        h_inv = torch.zeros(M, dtype=torch.float64, device="cuda:0")
-        ev = torch.zeros(M, dtype=torch.int32, device="cuda:0")
-        keep = (dev(slot[:M], torch.int32), dev(level[:M], torch.int32), dev(pwb[:M], torch.uint8), dev(dirs[:M], torch.float32),
-                dev(use_1d[:M], torch.uint8))
-        capi.check(lib.svo_hip_align_batch_counted(C.byref(store.layout), store.ptr, M, keep[0].data_ptr(), keep[1].data_ptr(),
-                                                   keep[2].data_ptr(), keep[3].data_ptr(), keep[4].data_ptr(), 10, px.data_ptr(),
-                                                   ok.data_ptr(), h_inv.data_ptr(), ev.data_ptr(), torch.cuda.current_stream().cuda_stream))
-        torch.cuda.synchronize()
-        return px.cpu().numpy(), ok.cpu().numpy(), h_inv.cpu().numpy(), ev.cpu().numpy()
-
-    px_w, ok_w, h_w, ev_w = run(M0)   # <= 8192 trials: the wave kernel
-    px_l, ok_l, h_l, ev_l = run(M1)   # beyond: the lane kernel
-    assert np.array_equal(ok_w, ok_l[:M0]) and np.array_equal(ev_w, ev_l[:M0])
-    assert np.array_equal(px_w.view(np.uint64), px_l[:M0].view(np.uint64))
-    assert np.array_equal(h_w.view(np.uint64), h_l[:M0].view(np.uint64))
-    assert ok_w.sum() > M0 // 4 and (ev_w == 10).sum() > 50 and (use_1d[:M0] > 0).sum() > 500
+    tr = tc.align_trials(case.checker(orc.which)[1], fuzz_rng(23), M1, 4.0)
+    wave = _counted(store, tr, M0)   # <= 8192 trials: the wave kernel
+    lane = _counted(store, tr, M1)   # beyond: the lane kernel
+    tc.same_alignment(wave, lane, M0)
+    ok_w, ev_w = wave[1], wave[3]
+    assert ok_w.sum() > M0 // 4 and (ev_w == 10).sum() > 50 and (tr["use_1d"][:M0] > 0).sum() > 500
 
 
-def test_phased_alignment_is_the_single_launch_bit_for_bit(gpu_device, scene, pyrs):
+def test_phased_alignment_is_the_single_launch_bit_for_bit(gpu_device, orc, case):
     """svo_hip_align_batch_phased (three launches, the unfinished trials compacted in between -- the form
     find_match_direct / update_seeds use for large batches) against the single launch on 73 728 trials: verdicts,
     refined pixels (bits), h_inv and evaluation counts identical.  The single launch itself is pinned to the
     reference by test_align_batch_bit_exact."""
-    store, _ = scene_store(scene)
+    store, _ = td.store_and_frames(case, case.T_f_w)
     rng = fuzz_rng(11)
     M0, REP = 3072, 24
-    imgs = scene.images.cpu().numpy()
-    slot = rng.integers(0, imgs.shape[0], size=M0).astype(np.int32)
-    level = rng.integers(0, 3, size=M0).astype(np.int32)
-    pwb = np.zeros((M0, 100), np.uint8)
-    px0 = np.zeros((M0, 2))
-    dirs = rng.normal(size=(M0, 2)).astype(np.float32)
-    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
-    use_1d = (rng.uniform(size=M0) < 0.3).astype(np.uint8)
-    for t in range(M0):
-        img = pyrs[slot[t]][level[t]]
-        h, w = img.shape
-        u, v = rng.integers(8, w - 8), rng.integers(8, h - 8)
-        src = pyrs[(slot[t] + (t % 2)) % imgs.shape[0]][level[t]]
-        pwb[t] = src[v - 5:v + 5, u - 5:u + 5].ravel()
-        px0[t] = [u + rng.uniform(-4.0, 4.0), v + rng.uniform(-4.0, 4.0)]  # far enough for many iterations
-        if t % 37 == 0:
-            px0[t] = [3.0 + rng.uniform(0, 2), v]
-        if t % 41 == 0:
-            pwb[t] = 77
+    tr = tc.align_trials(case.checker(orc.which)[1], rng, M0, 4.0)   # (starts far enough for many iterations)
     perm = rng.permutation(M0 * REP)  # copies of a trial land in different waves / queues
-    tile = lambda a: np.ascontiguousarray(np.tile(a, (REP,) + (1,) * (a.ndim - 1))[perm])
+    tr = {k: np.ascontiguousarray(np.tile(a, (REP,) + (1,) * (a.ndim - 1))[perm]) for k, a in tr.items()}
     M = M0 * REP
     assert capi.load().svo_hip_align_workspace_bytes(M) > 0  # large enough for the phased path
-    args = (store, dev(tile(slot), torch.int32), dev(tile(level), torch.int32), dev(tile(pwb), torch.uint8))
-    kw = dict(dir=dev(tile(dirs), torch.float32), use_1d=dev(tile(use_1d), torch.uint8))
-    px_a, px_b = dev(tile(px0), torch.float64), dev(tile(px0), torch.float64)
     ev_b = torch.zeros(M, dtype=torch.int32, device="cuda:0")
-    ok_a, h_a = tracking.align_batch(*args, px_a, 10, **kw)
-    ok_b, h_b = tracking.align_batch(*args, px_b, 10, phased=True, evaluations=ev_b, **kw)
-    ev_a = torch.zeros(M, dtype=torch.int32, device="cuda:0")
-    px_c = dev(tile(px0), torch.float64)
-    lib = capi.load()
-    import ctypes as C
-    ok_c = torch.zeros(M, dtype=torch.int32, device="cuda:0")
-    capi.check(lib.svo_hip_align_batch_counted(C.byref(store.layout), store.ptr, M, args[1].data_ptr(), args[2].data_ptr(),
-                                               args[3].data_ptr(), kw["dir"].data_ptr(), kw["use_1d"].data_ptr(), 10, px_c.data_ptr(),
-                                               ok_c.data_ptr(), None, ev_a.data_ptr(), torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    assert torch.equal(ok_a, ok_b)
-    assert np.array_equal(px_a.cpu().numpy().view(np.uint64), px_b.cpu().numpy().view(np.uint64))
-    assert np.array_equal(h_a.cpu().numpy().view(np.uint64), h_b.cpu().numpy().view(np.uint64))
-    assert torch.equal(ev_a, ev_b)
-    ev = ev_a.cpu().numpy()
+    single = td.align_batch(store, tr, 10)
+    phased = td.align_batch(store, tr, 10, phased=True, evaluations=ev_b)
+    tc.same_alignment(phased, single)
+    ev_a = _counted(store, tr, M, h_inv=False)[3]
+    ev = ev_b.cpu().numpy()
+    assert np.array_equal(ev_a, ev)
     assert (ev > 6).sum() > 100 and (ev <= 3).sum() > 100, np.bincount(ev)  # all three launches had work
 
 
-def test_find_match_direct(gpu_device, orc, scene, pyrs):
-    T = scene.T_f_w.copy()
-    T[scene.cur] = scene.T_cur_prior
-    store, frames = scene_store(scene, T_override=T)
-    P = len(scene.obs)
-    obs_ptr, fs = obs_csr(scene.obs)
-    m = tracking.Matcher(align_max_iter=10, n_pyr_levels=5)
-    res = m.find_match_direct(store, scene.cam, frames, torch.full((P,), scene.cur, dtype=torch.int32, device="cuda:0"),
-                              dev(scene.pt_pos, torch.float64), obs_ptr, fs, dev(scene.px_init, torch.float64))
-    torch.cuda.synchronize()
-    ok, px = res.ok.cpu().numpy(), res.px_cur.cpu().numpy()
-    ref_obs, sl = res.ref_obs.cpu().numpy(), res.search_level.cpu().numpy()
-    A, patches = res.A_cur_ref.cpu().numpy(), res.patch_with_border.cpu().numpy()
-    oframes = pytrack.make_frames(pyrs, T)
-    opt = pytrack.matcher_options(n_pyr_levels=5)
-    ptr = obs_ptr.cpu().numpy()
-    n_ok = n_edge = 0
-    for i in range(P):
-        obs = [pytrack.make_feature(*o) for o in scene.obs[i]]
-        o_ok, o_px, r = orc.find_match_direct(oframes, scene.cam, scene.cur, scene.pt_pos[i], obs, scene.px_init[i], opt)
-        assert bool(ok[i]) == o_ok, i
-        assert ref_obs[i] - ptr[i] == r["ref_obs"], i
-        if r["A_cur_ref"].any():
-            assert sl[i] == r["search_level"]
-            assert np.abs(A[i].reshape(2, 2) - r["A_cur_ref"]).max() < 1e-12      # f64 geometry
-            assert np.array_equal(patches[i], r["patch_with_border"]), i           # u8: identical
-        assert np.array_equal(px[i], o_px), (i, px[i], o_px)                       # float pipeline: identical
-        n_ok += o_ok
-        n_edge += o_ok and scene.obs[i][r["ref_obs"]][4] == 1
+def test_find_match_direct(gpu_device, orc, case):
+    worst = tc.verify_matcher(case, *td.find_match_direct(case), which=orc.which)
+    n_ok, n_edge = tc.matcher_coverage(case, orc.which)
+    print(f"find_match_direct[{orc.which}]: max |dA_cur_ref| {worst:.2e}")
     assert n_ok > 200 and n_edge > 20
 
 
-def test_reproject_points(gpu_device, orc, scene):
-    _, frames = scene_store(scene)
-    P = len(scene.pt_pos)
-    cell, px = tracking.reproject_points(scene.cam, frames, torch.full((P,), scene.cur, dtype=torch.int32, device="cuda:0"),
-                                         dev(scene.pt_pos, torch.float64), 30, 22)
-    cell, px = cell.cpu().numpy(), px.cpu().numpy()
-    for i in range(P):
-        k, p = orc.reproject_point(scene.cam, scene.T_f_w[scene.cur], scene.pt_pos[i], 30, 22)
-        assert k == cell[i] and np.abs(p - px[i]).max() < 1e-10
-    assert (cell >= 0).sum() > P // 2
+def test_reproject_points(gpu_device, orc, case):
+    tc.check_reproject_points(orc, case.scene, *td.reproject_points(case.scene))
 
 
-def test_pose_optimize_deferred(gpu_device, scene):
-    """svo_hip_pose_optimize_deferred = svo_hip_pose_optimize without the fix-up launch: same results on the frames
-    the wave kernel takes; the others come back untouched with ran == 2 and are finished by
-    svo_hip_pose_optimize_ordered.  n_iter = 0 is a documented hand-over (the kernel only reports the initial error
-    there), so it exercises that path for every frame."""
-    rng = fuzz_rng(4)
-    P = min(len(scene.pt_pos), 200)  # <= 256 observations per frame: the wave kernel's range
-    B = 6
-    pt_pos = scene.pt_pos[:P]
-    f = synth._bearing(scene.cam, scene.px_true[:P] + rng.normal(size=(P, 2)) * 0.3)
-    level = rng.integers(0, 3, size=P).astype(np.int32)
-    n = np.array([P, 150, 2, 64, 1, 40], dtype=np.int32)
-    hp = np.ones((B, P), dtype=np.uint8)
-    T0 = np.stack([se3.mul(se3.exp(rng.normal(size=6) * 5e-3), scene.T_f_w[scene.cur]) for _ in range(B)])
-
-    def run(n_iter, **kw):
-        r = tracking.optimize_gauss_newton(scene.cam, dev(n, torch.int32), dev(np.tile(f, (B, 1, 1)), torch.float64),
-                                           dev(np.tile(level, (B, 1)), torch.int32), dev(np.tile(pt_pos, (B, 1, 1)), torch.float64),
-                                           dev(hp, torch.uint8), dev(T0, torch.float64), 2.0, n_iter, **kw)
-        torch.cuda.synchronize()
-        return r.T_f_w.cpu().numpy(), r.ran.cpu().numpy(), r.has_point.cpu().numpy(), r.stats.cpu().numpy()
-
-    Tf, ran_f, hp_f, st_f = run(10)
-    Tp, ran_p, hp_p, st_p = run(10, deferred=True)
-    assert not (ran_f == 2).any()
-    taken = ran_p != 2
-    assert taken.any()
-    assert np.array_equal(Tf[taken], Tp[taken]) and np.array_equal(ran_f[taken], ran_p[taken]) and np.array_equal(hp_f[taken], hp_p[taken])
-    assert np.array_equal(Tp[~taken], T0[~taken]) and np.array_equal(hp_p[~taken], hp[~taken])          # untouched
-    # n_iter = 0: everything is handed over; the caller's second step gives what the one-call entry gives
-    T0f, ran0f, hp0f, st0f = run(0)
-    T0p, ran0p, hp0p, _ = run(0, deferred=True)
-    assert (ran0p == 2).all() and np.array_equal(T0p, T0) and np.array_equal(hp0p, hp)
-    T0o, ran0o, hp0o, st0o = run(0, ordered=True)
-    assert np.array_equal(T0o, T0f) and np.array_equal(ran0o, ran0f) and np.array_equal(hp0o, hp0f) and np.array_equal(st0o, st0f)
+def test_pose_optimize_deferred(gpu_device, case):
+    batch = tc.pose_deferred_batch(case.scene)
+    tc.check_pose_deferred(batch, lambda n_iter, entry: td.pose_optimize(case.scene.cam, batch, n_iter, entry))
 
 
 @pytest.mark.parametrize("ordered,row", [(True, 0), (False, 250), (False, 128), (False, 64)], ids=["ordered", "wave", "wave_rows_of_128", "wave_rows_of_64"])
-def test_pose_optimize(gpu_device, orc, scene, ordered, row):
-    """ordered=True: the checker kernel (normal equations summed in the reference's order).
-    ordered=False: the pipeline's wave kernel -- stated tolerance 1e-9 on the pose (SE(3) log norm),
-    identical pruning decisions and observation counts, medians to 1e-9 relative; frames whose
-    normal equations are singular (fewer observations than degrees of freedom) are handed to the
-    ordered kernel and therefore still match."""
-    rng = fuzz_rng(2)
-    # (the wave kernel takes rows of up to 256 observations -- svo_track::POSE_WAVE_MAX_STRIDE; a longer row goes to the
-    #  ordered kernel whatever the entry: the wave legs are given 250, 128 and 64 of the scene's 400 points -- the kernel's
-    #  instantiations with four, two and one observation per lane; the drop-in's frames of ~120 matches run the second)
-    P = len(scene.pt_pos) if ordered else min(len(scene.pt_pos), row)
-    B, ns = 12, P
-    f = synth._bearing(scene.cam, scene.px_true[:P] + rng.normal(size=(P, 2)) * 0.3)
-    level = rng.integers(0, 3, size=P).astype(np.int32)
-    pos = scene.pt_pos[:P].copy()
-    pos[::15] += rng.normal(size=pos[::15].shape) * 0.2
-    n = np.minimum(np.array([P, 200, 120, 40, 7, 3, P, P, 1, 150, 64, 5], dtype=np.int32), P).astype(np.int32)
-    hp = (rng.uniform(size=(B, ns)) > 0.2).astype(np.uint8)
-    hp[9] = 0                                                           # no observation has a point
-    T0 = np.stack([se3.mul(se3.exp(rng.normal(size=6) * 5e-3), scene.T_f_w[scene.cur]) for _ in range(B)])
-    n_iter = 10
-    res = tracking.optimize_gauss_newton(scene.cam, dev(n, torch.int32), dev(np.tile(f, (B, 1, 1)), torch.float64),
-                                         dev(np.tile(level, (B, 1)), torch.int32), dev(np.tile(pos, (B, 1, 1)), torch.float64),
-                                         dev(hp, torch.uint8), dev(T0, torch.float64), 2.0, n_iter, ordered=ordered)
-    torch.cuda.synchronize()
-    Tg, Cov, stats = res.T_f_w.cpu().numpy(), res.Cov.cpu().numpy(), res.stats.cpu().numpy()
-    ran, hpg = res.ran.cpu().numpy(), res.has_point.cpu().numpy()
-    devs = []
-    for b in range(B):
-        o = orc.pose_optimize(scene.cam, T0[b], f[:n[b]], level[:n[b]], hp[b, :n[b]], pos[:n[b]], 2.0, n_iter)
-        assert ran[b] == o["ran"], b
-        if not o["ran"]:
-            assert np.array_equal(Tg[b], T0[b]) and np.array_equal(hpg[b], hp[b])
-            continue
-        # f64 sums are formed in the reference's order; what differs is sin/cos in SE3::exp
-        if FUZZ and int(hp[b, :n[b]].sum()) < 6:
-            # (fewer than six observations: normal equations of rank < 6 or nearly so, where the reference's own answer is
-            #  decided by the rounding inside Eigen's pivoted LDLT -- on the committed scene both sides land on the same one;
-            #  on other scenes the requirement is that both ran and returned a pose)
-            assert np.isfinite(Tg[b]).all() == np.isfinite(o["T_f_w"]).all(), b
-            continue
-        # (wave kernel: 1e-15 on frames of 28 ... 250 observations, measured; the five to seven live observations of frame 4
-        #  -- ten to fourteen equations for six unknowns under Tukey weights -- amplify the summation order to 3e-9 ... 6e-9 on
-        #  three of twenty scenes; the pipeline gives up on a frame with fewer than Config::qualityMinFts = 50 features)
-        live = int(hp[b, :n[b]].sum())
-        # (one frame of 48 observations: 1.9e-9 -- at convergence chi2 moves in its last bits and "the error increased" is decided
-        #  by rounding on both sides; a decision that falls the other way leaves the size of the last Gauss-Newton step.  Hence
-        #  2e-8 per frame, and the MEDIAN over the batch's well-posed frames at 1e-12 below.)
-        dev_b = se3.log_norm(Tg[b][None], o["T_f_w"][None])[0]
-        if live >= 20:
-            devs.append(dev_b)
-        assert dev_b < (1e-10 if ordered else (2e-8 if live >= 20 else 1e-7)), b
-        assert np.array_equal(hpg[b, :n[b]], o["has_point"]), b
-        assert stats[b, 3] == o["num_obs"]
-        assert np.allclose(stats[b, :3], [o["estimated_scale"], o["error_init"], o["error_final"]], rtol=1e-9 if (ordered or (live >= 20 and dev_b < 1e-11)) else 1e-6, atol=1e-12)  # (the final error is the final pose's)
-        if n[b] >= 40:   # Cov of a well-conditioned system
-            assert np.allclose(Cov[b].reshape(6, 6), o["Cov"], rtol=1e-6, atol=1e-14), b
-    assert np.median(devs) < 1e-12, devs
-    assert se3.log_norm(Tg[0][None], scene.T_f_w[scene.cur][None])[0] < ((1.5e-2 if P >= 250 else 5e-2) if FUZZ else (2e-3 if P >= 250 else 5e-3))  # (vs ground truth: the scene's noise)
+def test_pose_optimize(gpu_device, orc, case, ordered, row):
+    """ordered=True: the checker kernel (normal equations summed in the reference's order).  ordered=False: the pipeline's
+    wave kernel on rows of 250, 128 and 64 observations.  The rule: tracking_cases.check_pose."""
+    batch, want = case.pose_ref(orc.which, ordered, row)
+    got = td.pose_optimize(case.scene.cam, batch, 10, "_ordered" if ordered else "")
+    devs = tc.check_pose_batch(case.scene, batch, want, got, ordered)
+    print(f"pose_optimize[{orc.which}, ordered={ordered}, row={row}]: max deviation over {len(devs)} frames of >= 20 live observations {max(devs):.2e}")
 
 
-def test_point_optimize(gpu_device, orc, scene):
-    _, frames = scene_store(scene)
-    rng = fuzz_rng(4)
-    obs_lists = scene.obs
-    ptr = np.zeros(len(obs_lists) + 1, dtype=np.int32)
-    fr, ff = [], []
-    for i, o in enumerate(obs_lists):
-        ptr[i + 1] = ptr[i] + len(o)
-        for x in o:
-            fr.append(x[0])
-            ff.append(x[2] + rng.normal(size=3) * 1e-3)
-    p0 = scene.pt_pos + rng.normal(size=scene.pt_pos.shape) * 0.05
-    out = tracking.point_optimize(frames, dev(ptr, torch.int32), dev(fr, torch.int32), dev(ff, torch.float64),
-                                  dev(p0, torch.float64), 5).cpu().numpy()
-    ff = np.array(ff)
-    for i in range(0, len(obs_lists), 3):
-        T = np.array([scene.T_f_w[x[0]] for x in obs_lists[i]])
-        o = orc.point_optimize(T, ff[ptr[i]:ptr[i + 1]], p0[i], 5)
-        assert np.abs(o - out[i]).max() < 1e-11, i
+def test_point_optimize(gpu_device, orc, case):
+    scene = case.scene
+    obs_ptr, fr, ff, p0 = tc.point_optimize_inputs(scene)
+    tc.check_point_optimize(orc, scene, obs_ptr, ff, p0, td.point_optimize(scene.T_f_w, obs_ptr, fr, ff, p0))
 
 
-def test_find_epipolar_match_direct(gpu_device, orc, scene, pyrs):
+def test_find_epipolar_match_direct(gpu_device, orc, case):
     """Matcher::findEpipolarMatchDirect on its own (the seam matcher.h:113-123 offers besides the depth
     filter): verdict and search level identical, px_cur_ to 1e-9, depth to 1e-9 relative."""
-    store, frames = scene_store(scene)
-    oframes = pytrack.make_frames(pyrs, scene.T_f_w)
-    rng = fuzz_rng(11)
-    feats, de, dmin, dmax = [], [], [], []
-    for i in range(0, len(scene.obs), 2):
-        o = [x for x in scene.obs[i] if x[0] != scene.cur][0]
-        c_ref = -scene.T_f_w[o[0], :9].reshape(3, 3).T @ scene.T_f_w[o[0], 9:]
-        d_true = np.linalg.norm(scene.pt_pos[i] - c_ref)
-        spread = [0.4, 0.1, 0.0005][(i // 2) % 3]
-        d_est = d_true * (1 + rng.normal() * spread * 0.3)
-        feats.append(o); de.append(d_est); dmin.append(d_est * (1 - spread)); dmax.append(d_est * (1 + spread))
-    S = len(feats)
-    fs = tracking.FeatureSet(frame=dev([o[0] for o in feats], torch.int32), level=dev([o[3] for o in feats], torch.int32),
-                             px=dev([o[1] for o in feats], torch.float64), f=dev([o[2] for o in feats], torch.float64),
-                             type=dev([o[4] for o in feats], torch.uint8), grad=dev([o[5] for o in feats], torch.float64))
     for align_1d in (0, 1):
-        ok, depth, px, lvl = tracking.find_epipolar_match_direct(
-            store, scene.cam, frames, torch.full((S,), scene.cur, dtype=torch.int32, device="cuda:0"), fs,
-            dev(de, torch.float64), dev(dmin, torch.float64), dev(dmax, torch.float64), n_pyr_levels=5, align_1d=bool(align_1d))
-        torch.cuda.synchronize()
-        ok, depth, px, lvl = ok.cpu().numpy(), depth.cpu().numpy(), px.cpu().numpy(), lvl.cpu().numpy()
-        opt = pytrack.matcher_options(n_pyr_levels=5, align_1d=align_1d)
-        n_ok = 0
-        for k in range(S):
-            ok_o, r = orc.find_epipolar_match_direct(oframes, scene.cam, feats[k][0], scene.cur, pytrack.make_feature(*feats[k]),
-                                                     de[k], dmin[k], dmax[k], opt)
-            assert bool(ok[k]) == ok_o, (k, ok[k], ok_o)
-            if ok_o:
-                n_ok += 1
-                assert lvl[k] == r["search_level"]
-                assert np.abs(px[k] - r["px_cur"]).max() < 1e-9 and abs(depth[k] - r["depth"]) < 1e-9 * abs(r["depth"])
-        assert n_ok > S // 3
+        wpx, wd = tc.verify_epipolar(case, align_1d, 1000, *td.find_epipolar(case, case.epi, align_1d, 1000), which=orc.which)
+        print(f"find_epipolar_match_direct[{orc.which}, align_1d={align_1d}]: max |dpx_cur| {wpx:.2e}, max relative depth difference {wd:.2e}")
+        assert sum(r[0] for r in case.epi_ref(orc.which, align_1d)) > case.epi.n // 3
 
 
 @pytest.mark.parametrize("cap", [6, 20])
-def test_max_epi_search_steps_cap(gpu_device, orc, scene, pyrs, cap):
-    """Matcher::Options::max_epi_search_steps below the scan length (matcher.cpp:248-256: "skip epipolar search",
-    `return false` before the first position is scored): the queries whose line is longer than `cap` steps fail, the others
-    are untouched by the cap -- verdict, search level, px_cur_ and depth like the checker's with the same cap, and the
-    cap really fired (queries that match at 1000 and not at `cap`)."""
-    store, frames = scene_store(scene)
-    oframes = pytrack.make_frames(pyrs, scene.T_f_w)
-    rng = fuzz_rng(23)
-    feats, de, dmin, dmax = [], [], [], []
-    for i in range(0, len(scene.obs), 2):
-        o = [x for x in scene.obs[i] if x[0] != scene.cur][0]
-        c_ref = -scene.T_f_w[o[0], :9].reshape(3, 3).T @ scene.T_f_w[o[0], 9:]
-        d_true = np.linalg.norm(scene.pt_pos[i] - c_ref)
-        spread = [0.5, 0.25, 0.05][(i // 2) % 3]
-        d_est = d_true * (1 + rng.normal() * spread * 0.2)
-        feats.append(o); de.append(d_est); dmin.append(d_est * (1 - spread)); dmax.append(d_est * (1 + spread))
-    S = len(feats)
-    fs = tracking.FeatureSet(frame=dev([o[0] for o in feats], torch.int32), level=dev([o[3] for o in feats], torch.int32),
-                             px=dev([o[1] for o in feats], torch.float64), f=dev([o[2] for o in feats], torch.float64),
-                             type=dev([o[4] for o in feats], torch.uint8), grad=dev([o[5] for o in feats], torch.float64))
-    cur = torch.full((S,), scene.cur, dtype=torch.int32, device="cuda:0")
-    run = lambda c: [t.cpu().numpy() for t in tracking.find_epipolar_match_direct(
-        store, scene.cam, frames, cur, fs, dev(de, torch.float64), dev(dmin, torch.float64), dev(dmax, torch.float64),
-        n_pyr_levels=5, max_epi_search_steps=c)]
-    ok_free, *_ = run(1000)
-    ok, depth, px, lvl = run(cap)
-    opt = pytrack.matcher_options(n_pyr_levels=5, max_epi_search_steps=cap)
-    opt_free = pytrack.matcher_options(n_pyr_levels=5)
-    n_ok = n_cut = 0
-    for k in range(S):
-        ok_o, r = orc.find_epipolar_match_direct(oframes, scene.cam, feats[k][0], scene.cur, pytrack.make_feature(*feats[k]),
-                                                 de[k], dmin[k], dmax[k], opt)
-        assert bool(ok[k]) == ok_o, (k, ok[k], ok_o)
-        if ok_o:
-            n_ok += 1
-            assert lvl[k] == r["search_level"]
-            assert np.abs(px[k] - r["px_cur"]).max() < 1e-9 and abs(depth[k] - r["depth"]) < 1e-9 * abs(r["depth"])
-        elif ok_free[k]:
-            ok_f, _ = orc.find_epipolar_match_direct(oframes, scene.cam, feats[k][0], scene.cur, pytrack.make_feature(*feats[k]),
-                                                     de[k], dmin[k], dmax[k], opt_free)
-            assert ok_f  # the checker, too, matches this query without the cap: the cap is what failed it
-            n_cut += 1
-            assert depth[k] == 0.0  # nothing of the match leaks out of a skipped search
-    assert n_cut >= 5 and n_ok >= 5, (n_cut, n_ok)
+def test_max_epi_search_steps_cap(gpu_device, orc, case, cap):
+    """Matcher::Options::max_epi_search_steps below the scan length: tracking_cases.verify_epipolar_cap."""
+    ok_free, *_ = td.find_epipolar(case, case.epi_cap, 0, 1000)
+    tc.verify_epipolar_cap(case, cap, ok_free, *td.find_epipolar(case, case.epi_cap, 0, cap), which=orc.which)
 
 
-def test_update_seeds_with_search_step_cap(gpu_device, orc, scene, pyrs):
-    """DepthFilter::updateSeeds with Matcher::Options::max_epi_search_steps = 8: a seed whose line is longer is a failed
-    match (b + 1, depth_filter.cpp:238-242), everything else as without the cap; statuses and seed state like the checker's."""
-    store, frames = scene_store(scene)
-    rng = fuzz_rng(8)
-    seeds, feats = _make_seeds(scene, orc, rng)
-    S = len(seeds)
-    oframes = pytrack.make_frames(pyrs, scene.T_f_w)
-    b_before = np.array([s.b for s in seeds], dtype=np.float32)
-    mk = lambda: (tracking.FeatureSet(frame=dev([o[0] for o in feats], torch.int32), level=dev([o[3] for o in feats], torch.int32),
-                                      px=dev([o[1] for o in feats], torch.float64), f=dev([o[2] for o in feats], torch.float64),
-                                      type=dev([o[4] for o in feats], torch.uint8), grad=dev([o[5] for o in feats], torch.float64)),
-                  tracking.SeedSet(a=dev([s.a for s in seeds], torch.float32), b=dev([s.b for s in seeds], torch.float32),
-                                   mu=dev([s.mu for s in seeds], torch.float32), z_range=dev([s.z_range for s in seeds], torch.float32),
-                                   sigma2=dev([s.sigma2 for s in seeds], torch.float32),
-                                   batch_id=dev([s.batch_id for s in seeds], torch.int32)))
-    cur = torch.full((S,), scene.cur, dtype=torch.int32, device="cuda:0")
-    res = {}
-    for cap in (1000, 8):
-        fs, ss = mk()
-        df = tracking.DepthFilter(n_pyr_levels=5, max_epi_search_steps=cap)
-        status, _, _ = df.update_seeds(store, scene.cam, frames, cur, fs, ss, batch_counter=5)
-        torch.cuda.synchronize()
-        res[cap] = (status.cpu().numpy(), ss.a.cpu().numpy(), ss.b.cpu().numpy(), ss.mu.cpu().numpy(), ss.sigma2.cpu().numpy())
-    # (the checker mutates its seed list: run it last)
-    opt = pytrack.matcher_options(n_pyr_levels=5, max_epi_search_steps=8)
-    nu, so, io = orc.update_seeds(oframes, scene.cam, scene.cur, seeds, batch_counter=5, opt=opt)
-    status, a, b, mu, s2 = res[8]
-    if orc.which == "ref":
-        status = np.where(np.isin(status, (pytrack.SEED_BEHIND, pytrack.SEED_NOT_IN_FRAME)), 0, status)
-    n_cut = 0
-    for i in range(S):
-        st = io[i].status
-        if st in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED):
-            margin = abs(np.sqrt(max(so[i].sigma2, 0.0)) * 200.0 / so[i].z_range - 1.0)
-            assert status[i] == st if margin > 1e-3 else status[i] in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED), (i, status[i], st)
-        else:
-            assert status[i] == st, (i, status[i], st)
-        if st == pytrack.SEED_NO_MATCH:
-            # it->b++ and nothing else
-            assert b[i] == np.float32(b_before[i] + np.float32(1.0)) and b[i] == np.float32(so[i].b)
-            assert a[i] == np.float32(so[i].a) and mu[i] == np.float32(so[i].mu) and s2[i] == np.float32(so[i].sigma2)
-            if res[1000][0][i] in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED):
-                n_cut += 1
-        elif st == pytrack.SEED_UPDATED:
-            assert np.isclose(mu[i], so[i].mu, rtol=2e-6, atol=0)
-    assert n_cut >= 5, n_cut
-
-
-def _make_seeds(scene, orc, rng):
-    seeds, feats = [], []
-    for i in range(len(scene.obs)):
-        o = [x for x in scene.obs[i] if x[0] != scene.cur][0]
-        c_ref = -scene.T_f_w[o[0], :9].reshape(3, 3).T @ scene.T_f_w[o[0], 9:]
-        d_true = np.linalg.norm(scene.pt_pos[i] - c_ref)
-        s = orc.seed_init(d_true * (1 + 0.1 * rng.normal()), d_true * 0.6)
-        s.ftr = pytrack.make_feature(*o)
-        s.batch_id = int(rng.integers(0, 6))
-        if i % 7 == 0:
-            s.sigma2 = np.float32(s.sigma2 * 7e-4)   # at the convergence threshold (sigma = z_range/227)
-        if i % 31 == 0:
-            s.mu = np.float32(-0.3)
-        if i % 5 == 0:
-            s.sigma2 = np.float32(s.sigma2 * 1e-3)   # sigma = z_range/190: short epipolar segment
-        seeds.append(s)
-        feats.append(o)
-    return seeds, feats
+def test_update_seeds_with_search_step_cap(gpu_device, orc, case):
+    """DepthFilter::updateSeeds with Matcher::Options::max_epi_search_steps = 8: tracking_cases.verify_seeds_cap."""
+    status_free, *_ = td.update_seeds(case, 0, 1, 1000)
+    tc.verify_seeds_cap(case, 8, status_free, *td.update_seeds(case, 0, 1, 8), which=orc.which)
 
 
 @pytest.mark.parametrize("align_1d,subpix", [(0, 1), (1, 1), (0, 0)])
-def test_update_seeds(gpu_device, orc, scene, pyrs, align_1d, subpix):
+def test_update_seeds(gpu_device, orc, case, align_1d, subpix):
     """subpix=0: Matcher::Options::subpix_refinement == false -- a scan match is triangulated straight
-    from uv_best (matcher.cpp:316-318) instead of being refined by align1D/align2D."""
-    store, frames = scene_store(scene)
-    rng = fuzz_rng(8)
-    seeds, feats = _make_seeds(scene, orc, rng)
-    S = len(seeds)
-    opt = pytrack.matcher_options(n_pyr_levels=5, align_1d=align_1d, subpix_refinement=subpix)
-    oframes = pytrack.make_frames(pyrs, scene.T_f_w)
-    nu, so, io = orc.update_seeds(oframes, scene.cam, scene.cur, seeds, batch_counter=5, opt=opt)
-    fs = tracking.FeatureSet(frame=dev([o[0] for o in feats], torch.int32), level=dev([o[3] for o in feats], torch.int32),
-                             px=dev([o[1] for o in feats], torch.float64), f=dev([o[2] for o in feats], torch.float64),
-                             type=dev([o[4] for o in feats], torch.uint8), grad=dev([o[5] for o in feats], torch.float64))
-    ss = tracking.SeedSet(a=dev([s.a for s in seeds], torch.float32), b=dev([s.b for s in seeds], torch.float32),
-                          mu=dev([s.mu for s in seeds], torch.float32), z_range=dev([s.z_range for s in seeds], torch.float32),
-                          sigma2=dev([s.sigma2 for s in seeds], torch.float32),
-                          batch_id=dev([s.batch_id for s in seeds], torch.int32))
-    df = tracking.DepthFilter(n_pyr_levels=5, align_1d=bool(align_1d), subpix_refinement=bool(subpix))
-    status, xyz, px = df.update_seeds(store, scene.cam, frames, torch.full((S,), scene.cur, dtype=torch.int32, device="cuda:0"),
-                                      fs, ss, batch_counter=5)
-    torch.cuda.synchronize()
-    status, xyz, px = status.cpu().numpy(), xyz.cpu().numpy(), px.cpu().numpy()
-    if orc.which == "ref":
-        # the reference's updateSeeds leaves no trace of "behind the camera" / "outside the image"
-        # (depth_filter.cpp:225-232: plain `continue`): its driver reports 0 for both
-        status = np.where(np.isin(status, (pytrack.SEED_BEHIND, pytrack.SEED_NOT_IN_FRAME)), 0, status)
-    a, b, mu, s2 = (t.cpu().numpy() for t in (ss.a, ss.b, ss.mu, ss.sigma2))
-    hist = {}
-    ab_dev = []
-    s2_dev = []  # measured deviation of sigma2: relative, and in units of float eps * mu^2
-    for i in range(S):
-        st = io[i].status
-        hist[st] = hist.get(st, 0) + 1
-        if st in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED):
-            # the convergence test sqrt(sigma2) < z_range/200 is a float threshold: only demand
-            # the same verdict when the oracle is not sitting on it
-            margin = abs(np.sqrt(max(so[i].sigma2, 0.0)) * 200.0 / so[i].z_range - 1.0)
-            if margin > 1e-3:
-                assert status[i] == st, (i, status[i], st)
-            else:
-                assert status[i] in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED)
-        else:
-            assert status[i] == st, (i, status[i], st)
-        # (a converged seed is erased from the reference's list; its driver recovers mu and sigma2 AFTER the last update
-        #  from what the converged callback is handed -- the variance, and the new point, whose distance from the seed's
-        #  frame is 1 / mu -- while a and b leave no trace there; the C port reports all four)
-        ab_known = not (orc.which == "ref" and st == pytrack.SEED_CONVERGED)
-        if st in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED, pytrack.SEED_NO_MATCH):
-            # Bayesian update: float arithmetic fed by an f64 depth that may differ in the last
-            # bits (the algebraic computeTau, exp) -- mu: 2e-6 relative.  sigma2 is formed as
-            # C1*(s2+m^2) + C2*(sigma2+mu^2) - mu_new^2 in float: a last-bit difference of its inputs shows as
-            # ~eps32 * mu^2 ABSOLUTE whatever sigma2's size.  MEASURED on the GPU (round 6, three cameras x three option
-            # sets x both checkers, printed below): 0 -- every sigma2 of this test has the checker's bits.  The bound
-            # is therefore what one last-bit input difference could cause (4 eps32 mu^2 + 4 eps32 sigma2), not the 1e-4
-            # sigma2 + 1e-6 mu^2 (0.7 % of a converged seed's sigma2) of rounds 2-5.
-            assert np.isclose(mu[i], so[i].mu, rtol=2e-6, atol=0), (i, mu[i], so[i].mu)
-            if so[i].sigma2 != 0 and so[i].mu != 0:
-                s2_dev.append((abs(float(s2[i]) - so[i].sigma2) / abs(so[i].sigma2), abs(float(s2[i]) - so[i].sigma2) / (6e-8 * so[i].mu ** 2)))
-            # (SVO_TEST_FUZZ=1..8, profiles/r06ad_*: up to 6.1 eps32 mu^2 on other scenes -- 1.4e-5 of sigma2 -- hence 16 eps32 there)
-            assert abs(float(s2[i]) - so[i].sigma2) <= (9.6e-7 if FUZZ else 2.4e-7) * (abs(so[i].sigma2) + so[i].mu ** 2), (i, s2[i], so[i].sigma2)
-            if ab_known:
-                ab_dev.append(max(abs(float(a[i]) - so[i].a) / abs(so[i].a), abs(float(b[i]) - so[i].b) / abs(so[i].b)))
-                assert np.allclose([a[i], b[i]], [so[i].a, so[i].b], rtol=AB_RTOL, atol=1e-5), (i, a[i], so[i].a, b[i], so[i].b)
-        if st in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED) and orc.which == "orc":
-            # (the reference's DepthFilter does not expose Matcher::px_cur_ per seed: C port only)
-            assert np.abs(px[i] - np.array(io[i].px_cur[:])).max() < 1e-9      # float alignment, identical start
-        if st == pytrack.SEED_CONVERGED:
-            assert np.abs(xyz[i] - np.array(io[i].xyz_world[:])).max() < 1e-5
+    from uv_best (matcher.cpp:316-318) instead of being refined by align1D/align2D.  In list order against the checker
+    (tracking_cases.verify_seeds, the device's sigma2 rule), then keyframe by keyframe (seed_order): the same bits."""
+    first = td.update_seeds(case, align_1d, subpix, 1000)
+    w = tc.verify_seeds(case, align_1d, subpix, 1000, *first, which=orc.which, device=True)
     print(f"update_seeds[{orc.which}, align_1d={align_1d}, subpix={subpix}]: max relative deviation of a / b over "
-          f"{len(ab_dev)} compared seeds = {max(ab_dev):.3e}; sigma2: max relative {max(x[0] for x in s2_dev):.3e}, "
-          f"max in units of eps32 * mu^2 {max(x[1] for x in s2_dev):.2f}")
-    assert hist.get(pytrack.SEED_UPDATED, 0) > 50 and hist.get(pytrack.SEED_CONVERGED, 0) > 2
-    assert hist.get(pytrack.SEED_ERASED_OLD, 0) > 5 and hist.get(pytrack.SEED_BEHIND if orc.which == "orc" else 0, 0) > 2
-    # The same seeds keyframe by keyframe, as a seed list holds them: a wave of seed_prepare_kernel then finds a handful of
-    # runs of equal (reference, current) pairs whose first seed files the pair's poses for seed_finish; in the order above
-    # the keyframe changes from seed to seed -- nearly every seed a run of its own.  The same bits either way.
-    fr = np.array([o[0] for o in feats])
-    order = np.argsort(fr, kind="stable")
-    assert np.count_nonzero(np.diff(fr) != 0) > 64 > np.count_nonzero(np.diff(fr[order]) != 0)
-    sel = lambda xs, dt: dev([xs[i] for i in order], dt)
-    fs2 = tracking.FeatureSet(frame=sel([o[0] for o in feats], torch.int32), level=sel([o[3] for o in feats], torch.int32),
-                              px=sel([o[1] for o in feats], torch.float64), f=sel([o[2] for o in feats], torch.float64),
-                              type=sel([o[4] for o in feats], torch.uint8), grad=sel([o[5] for o in feats], torch.float64))
-    seeds2, _ = _make_seeds(scene, orc, fuzz_rng(8))  # (the checker has updated `seeds` in place)
-    ss2 = tracking.SeedSet(a=sel([s.a for s in seeds2], torch.float32), b=sel([s.b for s in seeds2], torch.float32),
-                           mu=sel([s.mu for s in seeds2], torch.float32), z_range=sel([s.z_range for s in seeds2], torch.float32),
-                           sigma2=sel([s.sigma2 for s in seeds2], torch.float32), batch_id=sel([s.batch_id for s in seeds2], torch.int32))
-    status2, xyz2, px2 = df.update_seeds(store, scene.cam, frames, torch.full((S,), scene.cur, dtype=torch.int32, device="cuda:0"),
-                                         fs2, ss2, batch_counter=5)
-    torch.cuda.synchronize()
-    st2 = status2.cpu().numpy()
-    if orc.which == "ref":
-        st2 = np.where(np.isin(st2, (pytrack.SEED_BEHIND, pytrack.SEED_NOT_IN_FRAME)), 0, st2)
-    assert np.array_equal(st2, status[order]) and np.array_equal(px2.cpu().numpy(), px[order])
-    conv = status[order] == pytrack.SEED_CONVERGED
-    assert np.array_equal(xyz2.cpu().numpy()[conv], xyz[order][conv])
-    for got, want in zip((ss2.a, ss2.b, ss2.mu, ss2.sigma2), (a, b, mu, s2)):
-        assert np.array_equal(got.cpu().numpy(), want[order])
+          f"{w['n_ab']} compared seeds = {w['ab']:.3e}; sigma2: max relative {w['sigma2']:.3e}, "
+          f"max in units of eps32 * mu^2 {w['s2_eps']:.2f}")
+    tc.seed_coverage(case, orc.which, align_1d, subpix)
+    order = tc.seed_order(case)
+    tc.verify_seed_order(order, first, td.update_seeds(case, align_1d, subpix, 1000, order), which=orc.which)
 
 
-def test_update_seeds_on_the_resident_store(gpu_device, scene, pyrs, orc):
+def test_update_seeds_on_the_resident_store(gpu_device, case, orc):
     """Row N2, seeds: the seeds scattered over the slots of a resident store (svo_hip_seed_store_patch), updated through
-    svo_hip_update_seeds_resident in list order: statuses, new points, px_cur and the state -- in the store AND in the
-    dense read-back -- are the bits svo_hip_update_seeds produces on the flattened list; slots nobody named are untouched."""
-    store, frames = scene_store(scene)
-    rng = fuzz_rng(8)
-    seeds, feats = _make_seeds(scene, orc, rng)
-    S = len(seeds)
-    mk_f = lambda idx: tracking.FeatureSet(frame=dev([feats[i][0] for i in idx], torch.int32), level=dev([feats[i][3] for i in idx], torch.int32),
-                                           px=dev([feats[i][1] for i in idx], torch.float64), f=dev([feats[i][2] for i in idx], torch.float64),
-                                           type=dev([feats[i][4] for i in idx], torch.uint8), grad=dev([feats[i][5] for i in idx], torch.float64))
-    mk_s = lambda idx: tracking.SeedSet(a=dev([seeds[i].a for i in idx], torch.float32), b=dev([seeds[i].b for i in idx], torch.float32),
-                                        mu=dev([seeds[i].mu for i in idx], torch.float32), z_range=dev([seeds[i].z_range for i in idx], torch.float32),
-                                        sigma2=dev([seeds[i].sigma2 for i in idx], torch.float32),
-                                        batch_id=dev([seeds[i].batch_id for i in idx], torch.int32))
-    allidx = list(range(S))
-    # the flattened list through the plain entry point
-    fs, ss = mk_f(allidx), mk_s(allidx)
-    df = tracking.DepthFilter(n_pyr_levels=5)
-    st0, xyz0, px0 = df.update_seeds(store, scene.cam, frames, torch.full((S,), scene.cur, dtype=torch.int32, device="cuda:0"), fs, ss, batch_counter=5)
-    torch.cuda.synchronize()
-    # the same seeds in a store of 3 S slots, at random slots, patched in two instalments
-    cap = 3 * S
-    slots = rng.permutation(cap)[:S].astype(np.int32)
-    z = lambda n, dt: torch.full((n,) if isinstance(n, int) else n, 77, dtype=dt, device="cuda:0")
-    sf = tracking.FeatureSet(frame=z(cap, torch.int32), level=z(cap, torch.int32), px=z((cap, 2), torch.float64), f=z((cap, 3), torch.float64),
-                             type=z(cap, torch.uint8), grad=z((cap, 2), torch.float64))
-    sst = tracking.SeedSet(a=z(cap, torch.float32), b=z(cap, torch.float32), mu=z(cap, torch.float32), z_range=z(cap, torch.float32),
-                           sigma2=z(cap, torch.float32), batch_id=z(cap, torch.int32))
-    half = S // 2
-    for part in (allidx[:half], allidx[half:]):
-        tracking.DepthFilter.seed_store_patch(dev(slots[part], torch.int32), mk_f(part), mk_s(part), sf, sst)
-    st1, xyz1, px1, state = df.update_seeds_resident(store, scene.cam, frames, scene.cur, dev(slots, torch.int32), sf, sst, batch_counter=5)
-    torch.cuda.synchronize()
-    assert torch.equal(st0, st1) and torch.equal(px0, px1)
-    conv = st0 == pytrack.SEED_CONVERGED
-    assert torch.equal(xyz0[conv], xyz1[conv]) and int(conv.sum()) > 2
-    sl = torch.as_tensor(slots.astype(np.int64), device="cuda:0")
-    for name, k in (("a", 0), ("b", 1), ("mu", 2), ("sigma2", 3)):
-        flat, resident = getattr(ss, name), getattr(sst, name)[sl]
-        assert torch.equal(flat.view(torch.int32), resident.view(torch.int32)), name  # (bit patterns: NaN seeds included)
-        touched = torch.isin(st0, torch.tensor([pytrack.SEED_NO_MATCH, pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED, pytrack.SEED_NAN], device="cuda:0"))
-        assert torch.equal(state[k][touched].view(torch.int32), flat[touched].view(torch.int32)), name
-    free = torch.ones(cap, dtype=torch.bool, device="cuda:0")
-    free[sl] = False
-    assert (sst.mu[free] == 77).all() and (sf.level[free] == 77).all() and (sst.batch_id[free] == 77).all()
+    svo_hip_update_seeds_resident in list order: tracking_cases.verify_resident."""
+    S = case.P
+    st0, a, b, mu, s2, xyz0, px0 = td.update_seeds(case, 0, 1, 1000)
+    slots = tc.resident_slots(case)
+    resident = td.update_seeds_resident(case, slots, (np.arange(S // 2), np.arange(S // 2, S)))
+    _, conv = tc.verify_resident(slots, 3 * S, (st0, xyz0, px0, dict(a=a, b=b, mu=mu, sigma2=s2)), resident)
+    assert conv > 2
 
 
-def test_large_batches_take_the_same_decisions(gpu_device, scene, orc):
+def test_large_batches_take_the_same_decisions(gpu_device, case, orc):
     """Batches of >= 65 536 trials run the alignment in phases inside svo_hip_find_match_direct / svo_hip_update_seeds,
     and the epipolar scan orders the seeds of a workgroup by length: the same trials, tiled and shuffled into a large
     batch, must come back with the results of the small batch (which the tests above pin to the reference)."""
-    T = scene.T_f_w.copy()
-    T[scene.cur] = scene.T_cur_prior
-    store, frames = scene_store(scene, T_override=T)
+    scene, P = case.scene, case.P
+    store, frames = td.store_and_frames(case, case.T_match)
     rng = fuzz_rng(31)
     # -- findMatchDirect
-    P = len(scene.obs)
-    obs_ptr, fs = obs_csr(scene.obs)
+    fs, ptr_s = td.features(case.obs_cols), case.obs_ptr
     m = tracking.Matcher(align_max_iter=10, n_pyr_levels=5)
     cur = lambda n: torch.full((n,), scene.cur, dtype=torch.int32, device="cuda:0")
-    small = m.find_match_direct(store, scene.cam, frames, cur(P), dev(scene.pt_pos, torch.float64), obs_ptr, fs,
+    small = m.find_match_direct(store, scene.cam, frames, cur(P), dev(scene.pt_pos, torch.float64), dev(ptr_s, torch.int32), fs,
                                 dev(scene.px_init, torch.float64))
     rep = 65536 // P + 2
     order = rng.permutation(P * rep) % P                       # trial k of the large batch is trial order[k] of the small one
-    ptr_s = obs_ptr.cpu().numpy()
     cnt = (ptr_s[1:] - ptr_s[:-1])[order]
     ptr_l = np.zeros(len(order) + 1, dtype=np.int32)
     ptr_l[1:] = np.cumsum(cnt)
     gather = np.concatenate([np.arange(ptr_s[i], ptr_s[i + 1]) for i in order])
-    gi = torch.as_tensor(gather, device="cuda:0")
-    fs_l = tracking.FeatureSet(frame=fs.frame[gi].contiguous(), level=fs.level[gi].contiguous(), px=fs.px[gi].contiguous(),
-                               f=fs.f[gi].contiguous(), type=fs.type[gi].contiguous(), grad=fs.grad[gi].contiguous())
     big = tracking.Matcher(align_max_iter=10, n_pyr_levels=5).find_match_direct(
-        store, scene.cam, frames, cur(len(order)), dev(scene.pt_pos[order], torch.float64), dev(ptr_l, torch.int32), fs_l,
-        dev(scene.px_init[order], torch.float64))
+        store, scene.cam, frames, cur(len(order)), dev(scene.pt_pos[order], torch.float64), dev(ptr_l, torch.int32),
+        td.features(case.obs_cols, gather), dev(scene.px_init[order], torch.float64))
     torch.cuda.synchronize()
     oi = torch.as_tensor(order, device="cuda:0")
     assert torch.equal(big.ok, small.ok[oi]) and torch.equal(big.search_level, small.search_level[oi])
     assert np.array_equal(big.px_cur.cpu().numpy().view(np.uint64), small.px_cur[oi].cpu().numpy().view(np.uint64))
     assert torch.equal(big.patch_with_border, small.patch_with_border[oi])
-    # -- updateSeeds
-    seeds, feats = _make_seeds(scene, orc, rng)
-    S = len(seeds)
-    col = lambda f_, dt: dev([f_(x) for x in seeds], dt)
-
-    def run(idx):
-        n = len(idx)
-        ii = torch.as_tensor(idx, device="cuda:0")
-        fsd = tracking.FeatureSet(frame=dev([o[0] for o in feats], torch.int32)[ii].contiguous(), level=dev([o[3] for o in feats], torch.int32)[ii].contiguous(),
-                                  px=dev([o[1] for o in feats], torch.float64)[ii].contiguous(), f=dev([o[2] for o in feats], torch.float64)[ii].contiguous(),
-                                  type=dev([o[4] for o in feats], torch.uint8)[ii].contiguous(), grad=dev([o[5] for o in feats], torch.float64)[ii].contiguous())
-        ss = tracking.SeedSet(a=col(lambda s: s.a, torch.float32)[ii].contiguous(), b=col(lambda s: s.b, torch.float32)[ii].contiguous(),
-                              mu=col(lambda s: s.mu, torch.float32)[ii].contiguous(), z_range=col(lambda s: s.z_range, torch.float32)[ii].contiguous(),
-                              sigma2=col(lambda s: s.sigma2, torch.float32)[ii].contiguous(), batch_id=col(lambda s: s.batch_id, torch.int32)[ii].contiguous())
-        st, xyz, px = tracking.DepthFilter(n_pyr_levels=5).update_seeds(store, scene.cam, frames, cur(n), fsd, ss, batch_counter=5)
-        torch.cuda.synchronize()
-        return st, px, ss
-    st_s, px_s, ss_s = run(np.arange(S))
+    # -- updateSeeds (seeds of this test's own draws)
+    S = P
+    cols = tc.make_seeds(case.d_true, rng)
+    small = td.update_seeds(case, 0, 1, 1000, np.arange(S), cols)
     order = rng.permutation(S * (65536 // S + 2)) % S
-    st_l, px_l, ss_l = run(order)
-    oi = torch.as_tensor(order, device="cuda:0")
-    assert torch.equal(st_l, st_s[oi])
-    assert np.array_equal(px_l.cpu().numpy().view(np.uint64), px_s[oi].cpu().numpy().view(np.uint64))
-    for k in ("a", "b", "mu", "sigma2"):
-        assert np.array_equal(getattr(ss_l, k).cpu().numpy().view(np.uint32), getattr(ss_s, k)[oi].cpu().numpy().view(np.uint32)), k
+    large = td.update_seeds(case, 0, 1, 1000, order, cols)
+    bits = lambda x: np.ascontiguousarray(x).view(np.uint64 if x.dtype == np.float64 else np.uint32)
+    for k in (0, 1, 2, 3, 4, 6):   # status, a, b, mu, sigma2, px_cur
+        assert np.array_equal(bits(large[k]), bits(small[k][order])), k
 
 
 def test_update_seed_batch(gpu_device, orc):
-    rng = fuzz_rng(6)
-    S = 4000
-    seeds = []
-    for i in range(S):
-        s = orc.seed_init(rng.uniform(0.5, 5), rng.uniform(0.2, 0.5))
-        s.a, s.b = np.float32(rng.uniform(5, 30)), np.float32(rng.uniform(5, 30))
-        seeds.append(s)
-    x = (1.0 / rng.uniform(0.5, 5, size=S)).astype(np.float32)
-    tau2 = (10.0 ** rng.uniform(-8, 0, size=S)).astype(np.float32)
-    tau2[::50] = 0.0
-    x[::77] = 50.0
-    ss = tracking.SeedSet(a=dev([s.a for s in seeds], torch.float32), b=dev([s.b for s in seeds], torch.float32),
-                          mu=dev([s.mu for s in seeds], torch.float32), z_range=dev([s.z_range for s in seeds], torch.float32),
-                          sigma2=dev([s.sigma2 for s in seeds], torch.float32), batch_id=dev(np.zeros(S), torch.int32))
-    tracking.DepthFilter.update_seed(dev(x, torch.float32), dev(tau2, torch.float32), ss)
-    torch.cuda.synchronize()
-    got = np.stack([t.cpu().numpy() for t in (ss.a, ss.b, ss.mu, ss.sigma2)], axis=1).astype(np.float64)
-    want = np.array([[n.a, n.b, n.mu, n.sigma2] for n in (orc.update_seed(x[i], tau2[i], seeds[i]) for i in range(S))])
-    fin = np.isfinite(want).all(axis=1)
-    assert np.array_equal(np.isfinite(got).all(axis=1), fin)
-    # expf differs by an ulp between glibc and the GPU; a/b amplify it: (e-f)/(f-e/f) cancels
-    g, w = got[fin], want[fin]
-    assert np.allclose(g[:, 2], w[:, 2], rtol=2e-6, atol=0)                                   # mu
-    assert (np.abs(g[:, 3] - w[:, 3]) <= 1e-4 * np.abs(w[:, 3]) + 1e-6 * w[:, 2] ** 2).all()    # sigma2 (see above)
-    assert np.allclose(g[:, :2], w[:, :2], rtol=AB_RTOL_SAME_INPUTS, atol=0)                   # a, b
+    seeds, cols, x, tau2 = tc.seed_batch(orc, fuzz_rng(6), 4000)
+    tc.check_seed_batch(orc, seeds, x, tau2, td.update_seed_batch(cols, x, tau2))
 
 
 @pytest.mark.parametrize("kind", CAMERA_KINDS)
 def test_select_matches_like_the_cell_loop(gpu_device, kind):
-    """svo_hip_select_matches against the restated cell loop of Reprojector::reprojectMap (reprojector.cpp:131-139,
-    150-200): which trials become features, in which order, and the observation each one hands to the pose optimizer.
-    Indices / levels / positions identical; the bearing within 1e-14 (device tan / sqrt of the ATAN model)."""
+    """svo_hip_select_matches against the restated cell loop of Reprojector::reprojectMap: tracking_cases.check_select_matches."""
     cam = camera_models()[kind]
     rng = fuzz_rng(77)
-    for M, max_fts in ((0, 120), (1, 120), (7, 0), (130, 120), (300, 120), (300, 40), (1500, 120), (1500, 10000), (5000, 700)):
-        runs = rng.integers(1, 9, size=M + 1)
-        cell = np.repeat(rng.permutation(M + 1), runs)[:M].astype(np.int32)
-        ok = (rng.uniform(size=M) < 0.45).astype(np.int32)
-        px = np.stack([rng.uniform(0, cam.width, M), rng.uniform(0, cam.height, M)], axis=1).reshape(M, 2)
-        level = rng.integers(0, 4, size=M).astype(np.int32)
-        pos = rng.normal(size=(M, 3))
-        sel_o, f_o, lvl_o, pos_o = pytrack.select_matches(cam, cell, ok, px, level, pos, max_fts)
-        n, sel, f, lvl, p, has = tracking.select_matches(cam, dev(cell, torch.int32), dev(ok, torch.int32), dev(px, torch.float64),
-                                                         dev(level, torch.int32), dev(pos, torch.float64), max_fts)
-        k = int(n.item())
-        assert k == len(sel_o)
-        assert np.array_equal(sel[:k].cpu().numpy(), sel_o) and np.array_equal(lvl[:k].cpu().numpy(), lvl_o)
-        assert np.array_equal(p[:k].cpu().numpy(), pos_o) and bool((has[:k] == 1).all())
-        if k:
-            assert np.abs(f[:k].cpu().numpy() - f_o).max() <= 1e-14
+    for M, max_fts in tc.SELECT_SHAPES_DEVICE:
+        trials = tc.select_trials(cam, rng, M)
+        tc.check_select_matches(cam, trials, max_fts, *td.select_matches(cam, *trials, max_fts))
 
 
 @pytest.mark.gpu
@@ -786,40 +235,36 @@ def test_frame_pose_compose_is_the_hosts_product(gpu_device):
     """svo_hip_frame_pose_compose on the device: the bits of the host's SE3(R, t) * T_ref (IEEE f64 division and square root,
     no contraction) and the host's ranking of the overlapping keyframes, which is what lets the drop-in verify a chain
     enqueued behind K1 (test_entries_emulated.py has the statement-level twin on the CPU)."""
-    from rpg_svo_amd import capi
     from rpg_svo_amd.pyramid import _stream_ptr
-    import ctypes as C
-    from test_entries_emulated import (_composed_quat, _host_frame_pose, frame_pose_compose_cases, host_keyframe_ranks,
-                                       keyframe_rank_case)
     lib = capi.load()
     rng = fuzz_rng(5)
-    dev = torch.device(gpu_device)
-    td = lambda x, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(x), dtype=dt, device=dev)
-    for T, q, t in frame_pose_compose_cases(rng, 256):
+    device = torch.device(gpu_device)
+    td = lambda x, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(x), dtype=dt, device=device)
+    for T, q, t in tc.frame_pose_compose_cases(rng, 256):
         dT, dq, dt = td(T), td(q), td(t)
-        table = torch.zeros((3, 12), dtype=torch.float64, device=dev)
-        copy = torch.zeros(12, dtype=torch.float64, device=dev)
-        out = torch.zeros(12, dtype=torch.float64, device=dev)
-        sig = torch.zeros(1, dtype=torch.int32, device=dev)
+        table = torch.zeros((3, 12), dtype=torch.float64, device=device)
+        copy = torch.zeros(12, dtype=torch.float64, device=device)
+        out = torch.zeros(12, dtype=torch.float64, device=device)
+        sig = torch.zeros(1, dtype=torch.int32, device=device)
         capi.check(lib.svo_hip_frame_pose_compose(dT.data_ptr(), dq.data_ptr(), dt.data_ptr(), table.data_ptr(), 1, copy.data_ptr(),
                                                   out.data_ptr(), None, 0, 0, None, None, 0, None, None, sig.data_ptr(), 7,
-                                                  _stream_ptr(dev)), "svo_hip_frame_pose_compose")
+                                                  _stream_ptr(device)), "svo_hip_frame_pose_compose")
         torch.cuda.synchronize()
-        want = _host_frame_pose(T, q, t)
+        want = tc.host_frame_pose(T, q, t)
         assert np.array_equal(table[1].cpu().numpy(), want) and np.array_equal(copy.cpu().numpy(), want)
         assert np.array_equal(out.cpu().numpy(), want) and int(sig[0]) == 7
     cam = camera_models()["pinhole"]
     cs = capi.camera(cam)
     for trial in range(60):
-        table, key_pos, key_valid = keyframe_rank_case(rng)
+        table, key_pos, key_valid = tc.keyframe_rank_case(rng)
         n_tab, n_kf = len(table), len(key_pos)
         T = np.ascontiguousarray(se3.exp(rng.normal(size=6) * 0.05)); q = rng.normal(size=4); q /= np.linalg.norm(q); t = rng.normal(size=3) * 0.2
         for max_n in (3, 10):
-            tab = td(table); rank = torch.full((n_tab,), 99, dtype=torch.int32, device=dev); rank2 = rank.clone()
+            tab = td(table); rank = torch.full((n_tab,), 99, dtype=torch.int32, device=device); rank2 = rank.clone()
             dT, dq, dt, kp, kv = td(T), td(q), td(t), td(key_pos), td(key_valid, torch.uint8)
             capi.check(lib.svo_hip_frame_pose_compose(dT.data_ptr(), dq.data_ptr(), dt.data_ptr(), tab.data_ptr(), n_tab - 2, None, None,
                                                       C.byref(cs), n_tab, n_kf, kp.data_ptr(), kv.data_ptr(), max_n, rank.data_ptr(),
-                                                      rank2.data_ptr(), None, 0, _stream_ptr(dev)), "svo_hip_frame_pose_compose")
+                                                      rank2.data_ptr(), None, 0, _stream_ptr(device)), "svo_hip_frame_pose_compose")
             torch.cuda.synchronize()
-            want = host_keyframe_ranks(cam, _host_frame_pose(T, q, t), _composed_quat(T, q), key_pos, key_valid, tab.cpu().numpy(), n_kf, max_n)
+            want = tc.host_keyframe_ranks(cam, tc.host_frame_pose(T, q, t), tc.composed_quat(T, q), key_pos, key_valid, tab.cpu().numpy(), n_kf, max_n)
             assert np.array_equal(rank.cpu().numpy(), want) and np.array_equal(rank2.cpu().numpy(), want), (trial, rank, want)

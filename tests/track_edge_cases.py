@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE.  Scenes on which svo_hip_find_match_direct, svo_hip_find_epipolar_match_direct and
 svo_hip_update_seeds* leave the paths every other chain test stays on (synth.make_track_scene: feature level 0, search
 level 0, no feature near a border, A_cur_ref close to the identity, lines of at most 53 positions), a classifier in plain
-numpy that says which path of warp_group.h / depth_filter.hip / epi_scan.h a trial or seed takes, and the comparison
-rules of the existing tests.  tests/test_track_edges_emulated.py and tests/test_track_edges_gpu.py run the same cases.
+numpy that says which path of warp_group.h / depth_filter.hip / epi_scan.h a trial or seed takes.  A scene becomes a
+tests/tracking_cases.py Case, whose rules (verify_*) tests/test_track_edges_emulated.py and tests/test_track_edges_gpu.py apply.
 Everything a case expects -- results, classes, coverage -- comes from the checker (oracle.pytrack) and the classifier;
 neither calls the library under test.
 
@@ -129,15 +129,14 @@ import functools
 import numpy as np
 import torch
 
-from helpers import FUZZ, camera_models, fuzz_rng
+from helpers import FUZZ, camera_models
 from oracle import pyoracle, pytrack
 from rpg_svo_amd import se3, synth
+from tracking_cases import DEFAULT_SEED_MIN, DEFAULT_SPREADS, N_LEVELS, OK_SEED, Case
 
-N_LEVELS = 5
 N_KF, N_FEAT = 4, 100
 HEIGHT = 2.0
 MIN_OK, MIN_REJECTED = 20, 10     # coverage: successes per class / members of a class that is itself a rejection
-OK_SEED = (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED)
 SCAN_G, SCAN_PP, SCAN_BUCKETS, BOX_ROWS = 8, 16, 8, 20   # epi_scan.h, warp_group.h
 
 # name -> knobs of a scene.  poses: (height factor, lateral shift [m], direction of the shift [deg], roll [deg]) of the
@@ -158,7 +157,6 @@ CASES = {
     "E": dict(levels=(0, 0, 0, 1), kf_heights=(1.0, 1.0, 1.05, 0.95), pose=(0.62, 0.5, 0.0, 0.0), margin=110, cell=24,
               spreads=_log_cycle(0.0005, 0.6, 0.5, (0.5, 0.6)), seed_min=_log_cycle(100.0, 0.2, 0.5, (0.15, 0.2)), cap=200),
 }
-DEFAULT_SPREADS, DEFAULT_SEED_MIN = (0.4, 0.1, 0.0005), (0.6,)
 
 
 class Scene:
@@ -377,212 +375,128 @@ def line_uv(T_ref, T_cur, f, d_min, d_max, n_steps):
     return np.cumsum(np.vstack([B - step, np.tile(step, (n_steps, 1))]), axis=0)
 
 
-# ---- a case: scene, inputs, the checker's answers, classes ----------------------------------------------------------------
-class Case:
-    def __init__(self, name, cam_kind):
-        k = CASES[name]
-        self.name, self.cam_kind, self.knobs = name, cam_kind, k
-        self.scene = s = build_scene(camera_models()[cam_kind], **k)
-        self.P = len(s.obs)
-        self.cap = k.get("cap")
-        self._cache = {}
-        c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
-        # matcher inputs
-        T = s.T_f_w.copy()
-        T[s.cur] = s.T_cur_prior
-        self.T_match = np.ascontiguousarray(T)
-        self.obs_ptr = np.zeros(self.P + 1, np.int32)
-        flat = []
-        for i, o in enumerate(s.obs):
-            self.obs_ptr[i + 1] = self.obs_ptr[i] + len(o)
-            flat.extend(o)
-        cols = lambda fl: dict(frame=c([o[0] for o in fl], np.int32), level=c([o[3] for o in fl], np.int32), px=c([o[1] for o in fl], np.float64),
-                               f=c([o[2] for o in fl], np.float64), type=c([o[4] for o in fl], np.uint8), grad=c([o[5] for o in fl], np.float64))
-        self.obs_cols, self.ftr_cols = cols(flat), cols(s.feats)
-        # epipolar queries
-        rng = fuzz_rng(11)
-        spreads = k.get("spreads", DEFAULT_SPREADS)
-        sp = np.array([spreads[i % len(spreads)] for i in range(self.P)])
-        self.d_est = s.d_true * (1 + rng.normal(size=self.P) * sp * 0.3)
-        self.d_min, self.d_max = self.d_est * (1 - sp), self.d_est * (1 + sp)
-        # seeds (tests/test_tracking_gpu.py::_make_seeds, with the depth interval as a knob); SVO_TEST_FUZZ moves them
-        rng = fuzz_rng(8)
-        orc = pytrack.Track("orc")
-        smin = k.get("seed_min", DEFAULT_SEED_MIN)
-        seeds = []
-        for i in range(self.P):
-            sd = orc.seed_init(s.d_true[i] * (1 + 0.1 * rng.normal()), s.d_true[i] * smin[i % len(smin)])
-            sd.batch_id = int(rng.integers(0, 6))
-            if i % 7 == 0:
-                sd.sigma2 = np.float32(sd.sigma2 * 7e-4)   # at the convergence threshold
-            if i % 31 == 0:
-                sd.mu = np.float32(-0.3)
-            if i % 5 == 0:
-                sd.sigma2 = np.float32(sd.sigma2 * 1e-3)   # short segment
-            seeds.append(sd)
-        self.seed_cols = dict(a=c([x.a for x in seeds], np.float32), b=c([x.b for x in seeds], np.float32), mu=c([x.mu for x in seeds], np.float32),
-                              z_range=c([x.z_range for x in seeds], np.float32), sigma2=c([x.sigma2 for x in seeds], np.float32),
-                              batch_id=c([x.batch_id for x in seeds], np.int32))
+# ---- a case: a scene of build_scene as a tracking_cases.Case, and its classes (orc checker + classifier) ---------------------
+def _level_size(c, level):
+    return c.scene.images.shape[2] >> level, c.scene.images.shape[1] >> level
 
-    # -- the checker ---------------------------------------------------------------------------------------------------
-    def _memo(self, key, fn):
-        if key not in self._cache:
-            self._cache[key] = fn()
-        return self._cache[key]
 
-    def checker(self, which):
-        def make():
-            orc = pytrack.Track(which)
-            pyrs = [orc.create_img_pyramid(im, N_LEVELS) for im in self.scene.images]
-            return orc, pyrs, pytrack.make_frames(pyrs, self.T_match), pytrack.make_frames(pyrs, self.scene.T_f_w)
-        return self._memo(("checker", which), make)
+def matcher_classes(c):
+    """per trial: dict(ok, levels=(ref level, search level) or None, warp, border_rejected)"""
+    def run():
+        s, out = c.scene, []
+        for i, (ok, _, r) in enumerate(c.matcher_ref()):
+            o = s.obs[i][r["ref_obs"]]
+            rl = o[3]
+            wl, hl = s.cam.width // (1 << rl), s.cam.height // (1 << rl)
+            x, y = int(o[1][0]) // (1 << rl), int(o[1][1]) // (1 << rl)   # (int(): towards zero, as the cast)
+            if o[1][0] < 0 or o[1][1] < 0:
+                x, y = -1, -1
+            inside = 6 <= x < wl - 6 and 6 <= y < hl - 6
+            reached = bool(r["A_cur_ref"].any())
+            assert reached <= inside
+            d = dict(ok=ok, levels=None, warp=None, border_rejected=not inside, ref_level=rl)
+            if reached:
+                d["levels"] = (rl, r["search_level"])
+                d["warp"] = warp_path(r["A_cur_ref"], o[1], rl, r["search_level"], *_level_size(c, rl))
+            out.append(d)
+        return out
+    return c._memo("matcher_classes", run)
 
-    def matcher_ref(self, which="orc"):
-        def run():
-            orc, _, fm, _ = self.checker(which)
-            s, opt = self.scene, pytrack.matcher_options(n_pyr_levels=N_LEVELS)
-            return [orc.find_match_direct(fm, s.cam, s.cur, s.pt_pos[i], [pytrack.make_feature(*x) for x in s.obs[i]], s.px_init[i], opt)
-                    for i in range(self.P)]
-        return self._memo(("matcher", which), run)
 
-    def epi_ref(self, which="orc", align_1d=0, cap=1000):
-        def run():
-            orc, _, _, ft = self.checker(which)
-            s, opt = self.scene, pytrack.matcher_options(n_pyr_levels=N_LEVELS, align_1d=align_1d, max_epi_search_steps=cap)
-            return [orc.find_epipolar_match_direct(ft, s.cam, s.feats[k][0], s.cur, pytrack.make_feature(*s.feats[k]), self.d_est[k],
-                                                   self.d_min[k], self.d_max[k], opt) for k in range(self.P)]
-        return self._memo(("epi", which, align_1d, cap), run)
+def line_classes(c, kind):
+    """kind "epi" (the queries) or "seeds".  per entry: dict(ok, levels, warp, mode: "none" / "short" / "scan" / "cap",
+    n_steps, bucket, passes: set of pass kinds) -- the line itself from the checker's findEpipolarMatchDirect on the
+    entry's depth interval (A_cur_ref, search level, epi_length)"""
+    def run():
+        s = c.scene
+        orc, _, _, ft = c.checker("orc")
+        w2c = oracle_world2cam(s.cam)
+        opt = pytrack.matcher_options(n_pyr_levels=N_LEVELS)
+        out = []
+        if kind == "epi":
+            res = c.epi_ref()
+            oks = [ok for ok, _ in res]
+            lines = [(c.epi.d_est[k], c.epi.d_min[k], c.epi.d_max[k], res[k][1]) for k in range(c.P)]
+        else:
+            so, io = c.seeds_ref()
+            oks = [x.status in OK_SEED for x in io]
+            lines = []
+            sc = c.seed_cols
+            for k in range(c.P):
+                if io[k].status in (pytrack.SEED_ERASED_OLD, pytrack.SEED_BEHIND, pytrack.SEED_NOT_IN_FRAME):
+                    lines.append(None)
+                    continue
+                mu, sq = sc["mu"][k], np.sqrt(sc["sigma2"][k])
+                zlo = np.float32(mu - sq)
+                d = (1.0 / float(mu), 1.0 / float(np.float32(mu + sq)), 1.0 / float(zlo if zlo >= np.float32(1e-8) else np.float32(1e-8)))
+                _, r = orc.find_epipolar_match_direct(ft, s.cam, c.feats[k][0], s.cur, pytrack.make_feature(*c.feats[k]), *d, opt)
+                lines.append((*d, r))
+        for k in range(c.P):
+            d = dict(ok=bool(oks[k]), levels=None, warp=None, mode="none", n_steps=0, bucket=None, passes=set())
+            if lines[k] is not None and not lines[k][3]["reject"]:
+                de, dmin, dmax, r = lines[k]
+                o = c.feats[k]
+                sl = r["search_level"]
+                d["levels"] = (o[3], sl)
+                d["warp"] = warp_path(r["A_cur_ref"], o[1], o[3], sl, *_level_size(c, o[3]))
+                el = r["epi_length"]
+                if el < 2.0:
+                    d["mode"], d["bucket"] = "short", 0
+                elif not np.isfinite(el) or int(el / 0.7) > 1000:
+                    d["mode"], d["n_steps"] = "cap", (int(el / 0.7) if np.isfinite(el) else -1)
+                else:
+                    n = int(el / 0.7)
+                    d["mode"], d["n_steps"], d["bucket"] = "scan", n, scan_bucket(n)
+                    uv = line_uv(s.T_f_w[o[0]], s.T_f_w[s.cur], o[2], dmin, dmax, n)
+                    d["passes"] = set(scan_pass_kinds(w2c(uv), sl, s.cam.width, s.cam.height))
+            out.append(d)
+        return out
+    return c._memo(("line_classes", kind), run)
 
-    def seeds_ref(self, which="orc", align_1d=0, subpix=1, cap=1000):
-        def run():
-            orc, _, _, ft = self.checker(which)
-            s, sc = self.scene, self.seed_cols
-            seeds = []
-            for i in range(self.P):
-                sd = pytrack.Seed()
-                sd.ftr = pytrack.make_feature(*s.feats[i])
-                sd.batch_id, sd.a, sd.b, sd.mu = int(sc["batch_id"][i]), sc["a"][i], sc["b"][i], sc["mu"][i]
-                sd.z_range, sd.sigma2 = sc["z_range"][i], sc["sigma2"][i]
-                seeds.append(sd)
-            opt = pytrack.matcher_options(n_pyr_levels=N_LEVELS, align_1d=align_1d, subpix_refinement=subpix, max_epi_search_steps=cap)
-            _, so, io = orc.update_seeds(ft, s.cam, s.cur, seeds, batch_counter=5, opt=opt)
-            return so, io
-        return self._memo(("seeds", which, align_1d, subpix, cap), run)
 
-    # -- classes (orc checker + classifier) ------------------------------------------------------------------------------
-    def _level_size(self, level):
-        return self.scene.images.shape[2] >> level, self.scene.images.shape[1] >> level
+def counts(c):
+    """the class counts of the docstring: name -> (members, of which the checker succeeds)"""
+    def run():
+        cnt = {}
 
-    def matcher_classes(self):
-        """per trial: dict(ok, levels=(ref level, search level) or None, warp, border_rejected)"""
-        def run():
-            s, out = self.scene, []
-            for i, (ok, _, r) in enumerate(self.matcher_ref()):
-                o = s.obs[i][r["ref_obs"]]
-                rl = o[3]
-                wl, hl = s.cam.width // (1 << rl), s.cam.height // (1 << rl)
-                x, y = int(o[1][0]) // (1 << rl), int(o[1][1]) // (1 << rl)   # (int(): towards zero, as the cast)
-                if o[1][0] < 0 or o[1][1] < 0:
-                    x, y = -1, -1
-                inside = 6 <= x < wl - 6 and 6 <= y < hl - 6
-                reached = bool(r["A_cur_ref"].any())
-                assert reached <= inside
-                d = dict(ok=ok, levels=None, warp=None, border_rejected=not inside, ref_level=rl)
-                if reached:
-                    d["levels"] = (rl, r["search_level"])
-                    d["warp"] = warp_path(r["A_cur_ref"], o[1], rl, r["search_level"], *self._level_size(rl))
-                out.append(d)
-            return out
-        return self._memo("matcher_classes", run)
-
-    def line_classes(self, kind):
-        """kind "epi" (the queries) or "seeds".  per entry: dict(ok, levels, warp, mode: "none" / "short" / "scan" / "cap",
-        n_steps, bucket, passes: set of pass kinds) -- the line itself from the checker's findEpipolarMatchDirect on the
-        entry's depth interval (A_cur_ref, search level, epi_length)"""
-        def run():
-            s = self.scene
-            orc, _, _, ft = self.checker("orc")
-            w2c = oracle_world2cam(s.cam)
-            opt = pytrack.matcher_options(n_pyr_levels=N_LEVELS)
-            out = []
-            if kind == "epi":
-                res = self.epi_ref()
-                oks = [ok for ok, _ in res]
-                lines = [(self.d_est[k], self.d_min[k], self.d_max[k], res[k][1]) for k in range(self.P)]
-            else:
-                so, io = self.seeds_ref()
-                oks = [x.status in OK_SEED for x in io]
-                lines = []
-                sc = self.seed_cols
-                for k in range(self.P):
-                    if io[k].status in (pytrack.SEED_ERASED_OLD, pytrack.SEED_BEHIND, pytrack.SEED_NOT_IN_FRAME):
-                        lines.append(None)
-                        continue
-                    mu, sq = sc["mu"][k], np.sqrt(sc["sigma2"][k])
-                    zlo = np.float32(mu - sq)
-                    d = (1.0 / float(mu), 1.0 / float(np.float32(mu + sq)), 1.0 / float(zlo if zlo >= np.float32(1e-8) else np.float32(1e-8)))
-                    _, r = orc.find_epipolar_match_direct(ft, s.cam, s.feats[k][0], s.cur, pytrack.make_feature(*s.feats[k]), *d, opt)
-                    lines.append((*d, r))
-            for k in range(self.P):
-                d = dict(ok=bool(oks[k]), levels=None, warp=None, mode="none", n_steps=0, bucket=None, passes=set())
-                if lines[k] is not None and not lines[k][3]["reject"]:
-                    de, dmin, dmax, r = lines[k]
-                    o = s.feats[k]
-                    sl = r["search_level"]
-                    d["levels"] = (o[3], sl)
-                    d["warp"] = warp_path(r["A_cur_ref"], o[1], o[3], sl, *self._level_size(o[3]))
-                    el = r["epi_length"]
-                    if el < 2.0:
-                        d["mode"], d["bucket"] = "short", 0
-                    elif not np.isfinite(el) or int(el / 0.7) > 1000:
-                        d["mode"], d["n_steps"] = "cap", (int(el / 0.7) if np.isfinite(el) else -1)
-                    else:
-                        n = int(el / 0.7)
-                        d["mode"], d["n_steps"], d["bucket"] = "scan", n, scan_bucket(n)
-                        uv = line_uv(s.T_f_w[o[0]], s.T_f_w[s.cur], o[2], dmin, dmax, n)
-                        d["passes"] = set(scan_pass_kinds(w2c(uv), sl, s.cam.width, s.cam.height))
-                out.append(d)
-            return out
-        return self._memo(("line_classes", kind), run)
-
-    def counts(self):
-        """the class counts of the docstring: name -> (members, of which the checker succeeds)"""
-        def run():
-            cnt = {}
-
-            def add(key, ok):
-                m, n = cnt.get(key, (0, 0))
-                cnt[key] = (m + 1, n + int(bool(ok)))
-            for d in self.matcher_classes():
-                if d["border_rejected"]:
-                    add("match border-rejected", False)
-                    if d["ref_level"] > 0:
-                        add("match border-rejected above level 0", False)
-                if d["levels"]:
-                    add(f"match levels {d['levels']}", d["ok"])
-                    add(f"match sl {d['levels'][1]}", d["ok"])
-                    add("match sl " + ("above" if d["levels"][1] > d["levels"][0] else "equal" if d["levels"][1] == d["levels"][0] else "below") + " ref", d["ok"])
-                    add(f"match warp {d['warp']}", d["ok"])
-            for kind in ("epi", "seeds"):
-                for d in self.line_classes(kind):
-                    if not d["levels"]:
-                        continue
-                    add(f"{kind} levels {d['levels']}", d["ok"])
-                    add(f"{kind} sl {d['levels'][1]}", d["ok"])
-                    add(f"{kind} sl " + ("above" if d["levels"][1] > d["levels"][0] else "equal" if d["levels"][1] == d["levels"][0] else "below") + " ref", d["ok"])
-                    add(f"{kind} warp {d['warp']}", d["ok"])
-                    add(f"{kind} mode {d['mode']}", d["ok"])
-                    if d["mode"] == "scan":
-                        add(f"{kind} bucket {d['bucket']}", d["ok"])
-                        for p in d["passes"]:
-                            add(f"{kind} pass {p}", d["ok"])
-            return cnt
-        return self._memo("counts", run)
+        def add(key, ok):
+            m, n = cnt.get(key, (0, 0))
+            cnt[key] = (m + 1, n + int(bool(ok)))
+        for d in matcher_classes(c):
+            if d["border_rejected"]:
+                add("match border-rejected", False)
+                if d["ref_level"] > 0:
+                    add("match border-rejected above level 0", False)
+            if d["levels"]:
+                add(f"match levels {d['levels']}", d["ok"])
+                add(f"match sl {d['levels'][1]}", d["ok"])
+                add("match sl " + ("above" if d["levels"][1] > d["levels"][0] else "equal" if d["levels"][1] == d["levels"][0] else "below") + " ref", d["ok"])
+                add(f"match warp {d['warp']}", d["ok"])
+        for kind in ("epi", "seeds"):
+            for d in line_classes(c, kind):
+                if not d["levels"]:
+                    continue
+                add(f"{kind} levels {d['levels']}", d["ok"])
+                add(f"{kind} sl {d['levels'][1]}", d["ok"])
+                add(f"{kind} sl " + ("above" if d["levels"][1] > d["levels"][0] else "equal" if d["levels"][1] == d["levels"][0] else "below") + " ref", d["ok"])
+                add(f"{kind} warp {d['warp']}", d["ok"])
+                add(f"{kind} mode {d['mode']}", d["ok"])
+                if d["mode"] == "scan":
+                    add(f"{kind} bucket {d['bucket']}", d["ok"])
+                    for p in d["passes"]:
+                        add(f"{kind} pass {p}", d["ok"])
+        return cnt
+    return c._memo("counts", run)
 
 
 @functools.lru_cache(maxsize=None)
 def case(name, cam_kind):
-    return Case(name, cam_kind)
+    k = CASES[name]
+    s = build_scene(camera_models()[cam_kind], **k)
+    c = Case(name, s, s.feats, s.d_true, spreads=k.get("spreads", DEFAULT_SPREADS), seed_min=k.get("seed_min", DEFAULT_SEED_MIN), cap=k.get("cap"),
+             cam_kind=cam_kind, knobs=k)
+    c.describe = lambda kind, i: (matcher_classes(c) if kind == "matcher" else line_classes(c, kind))[i]
+    return c
 
 
 def format_counts(cnt):
@@ -612,7 +526,7 @@ COVERAGE_ATAN_E = [("lines pass half", MIN_OK)]
 def group_counts(group, cam_kind):
     total = {}
     for name in COVERAGE[group][0]:
-        for k, (m, n) in case(name, cam_kind).counts().items():
+        for k, (m, n) in counts(case(name, cam_kind)).items():
             keys = [k]
             if k.startswith(("epi ", "seeds ")):
                 keys.append("lines " + k.split(" ", 1)[1])
@@ -636,80 +550,3 @@ def assert_coverage(group, cam_kind):
     for k, n in need_members:
         assert cnt.get(k, (0, 0))[0] >= n, f"{group} {cam_kind}: class '{k}' has {cnt.get(k, (0, 0))[0]} members, needs {n}"
     return cnt
-
-
-# ---- comparison rules: those of the existing tests, unchanged -----------------------------------------------------------------
-def verify_matcher(c, ok, px, ref_obs, sl, A, patches, which="orc"):
-    """tests/test_tracking_gpu.py::test_find_match_direct: verdict, chosen observation, search level, patch bytes and refined
-    pixel identical, A_cur_ref to 1e-12.  ref_obs: index into the flattened observations.  Returns the largest |dA|."""
-    worst = 0.0
-    for i, (o_ok, o_px, r) in enumerate(c.matcher_ref(which)):
-        assert bool(ok[i]) == o_ok, (c.name, i)
-        assert ref_obs[i] - c.obs_ptr[i] == r["ref_obs"], (c.name, i)
-        if r["A_cur_ref"].any():
-            assert sl[i] == r["search_level"], (c.name, i, sl[i], r["search_level"])
-            dA = np.abs(A[i].reshape(2, 2) - r["A_cur_ref"]).max()
-            worst = max(worst, dA)
-            assert dA < 1e-12, (c.name, i, dA)
-            assert np.array_equal(patches[i], r["patch_with_border"]), (c.name, i, c.matcher_classes()[i] if which == "orc" else None)
-        assert np.array_equal(px[i], o_px), (c.name, i, px[i], o_px)
-    return worst
-
-
-def verify_epipolar(c, align_1d, cap, ok, depth, px, lvl, which="orc"):
-    """tests/test_tracking_gpu.py::test_find_epipolar_match_direct: verdict and search level identical, px_cur to 1e-9, depth
-    to 1e-9 relative.  Returns (largest |dpx|, largest relative depth difference)."""
-    wpx = wd = 0.0
-    for k, (ok_o, r) in enumerate(c.epi_ref(which, align_1d, cap)):
-        assert bool(ok[k]) == ok_o, (c.name, k, ok[k], ok_o, c.line_classes("epi")[k])
-        if ok_o:
-            assert lvl[k] == r["search_level"], (c.name, k)
-            dpx, dd = np.abs(px[k] - r["px_cur"]).max(), abs(depth[k] - r["depth"]) / abs(r["depth"])
-            wpx, wd = max(wpx, dpx), max(wd, dd)
-            assert dpx < 1e-9 and dd < 1e-9, (c.name, k, dpx, dd, c.line_classes("epi")[k])
-    return wpx, wd
-
-
-def verify_seeds(c, align_1d, subpix, cap, status, a, b, mu, s2, xyz, px, which="orc", device=False):
-    """device=False: tests/test_track_emulated.py::test_emulated_update_seeds; device=True: tests/test_tracking_gpu.py::
-    test_update_seeds (the rule for a seed on the convergence threshold and the "ref" checker's status mapping included).
-    Returns dict(mu, sigma2, ab, px): the largest relative deviations (px absolute)."""
-    so, io = c.seeds_ref(which, align_1d, subpix, cap)
-    if which == "ref":
-        # the reference's updateSeeds leaves no trace of "behind the camera" / "outside the image": its driver reports 0 for both
-        status = np.where(np.isin(status, (pytrack.SEED_BEHIND, pytrack.SEED_NOT_IN_FRAME)), 0, status)
-    w = dict(mu=0.0, sigma2=0.0, ab=0.0, px=0.0)
-    for i in range(c.P):
-        st = io[i].status
-        tag = (c.name, i, int(status[i]), st)
-        if st in OK_SEED:
-            margin = abs(np.sqrt(max(so[i].sigma2, 0.0)) * 200.0 / so[i].z_range - 1.0)
-            if margin > 1e-3:
-                assert status[i] == st, tag
-            else:
-                assert status[i] in OK_SEED, tag
-        else:
-            assert status[i] == st, tag
-        ab_known = not (which == "ref" and st == pytrack.SEED_CONVERGED)
-        if st in (pytrack.SEED_UPDATED, pytrack.SEED_CONVERGED, pytrack.SEED_NO_MATCH):
-            assert np.isclose(mu[i], so[i].mu, rtol=2e-6, atol=0), (tag, mu[i], so[i].mu)
-            ds2 = abs(float(s2[i]) - so[i].sigma2)
-            if device:
-                assert ds2 <= (9.6e-7 if FUZZ else 2.4e-7) * (abs(so[i].sigma2) + so[i].mu ** 2), (tag, s2[i], so[i].sigma2)
-            else:
-                assert ds2 <= 1e-4 * abs(so[i].sigma2) + 1e-6 * so[i].mu ** 2, (tag, s2[i], so[i].sigma2)
-            if so[i].mu != 0:
-                w["mu"] = max(w["mu"], abs(float(mu[i]) - so[i].mu) / abs(so[i].mu))
-            if so[i].sigma2 != 0:
-                w["sigma2"] = max(w["sigma2"], ds2 / abs(so[i].sigma2))
-            if ab_known:
-                w["ab"] = max(w["ab"], abs(float(a[i]) - so[i].a) / abs(so[i].a), abs(float(b[i]) - so[i].b) / abs(so[i].b))
-                assert np.allclose([a[i], b[i]], [so[i].a, so[i].b], rtol=1e-4, atol=1e-5), (tag, a[i], so[i].a, b[i], so[i].b)
-        if st in OK_SEED and which == "orc":
-            # (the reference's DepthFilter does not expose Matcher::px_cur_ per seed: C port only)
-            dpx = np.abs(px[i] - np.array(io[i].px_cur[:])).max()
-            w["px"] = max(w["px"], dpx)
-            assert dpx < 1e-9, (tag, dpx)
-        if st == pytrack.SEED_CONVERGED:
-            assert np.abs(xyz[i] - np.array(io[i].xyz_world[:])).max() < 1e-5, tag
-    return w
