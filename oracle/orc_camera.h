@@ -15,6 +15,14 @@
  *  ORC_CAM_ATAN            vk::ATANCamera (FOV model of PTAM); fx, fy, cx, cy are the constructor's
  *                          fx_ = width*fx, fy_ = height*fy, cx_ = cx*width - 0.5, cy_ = cy*height - 0.5;
  *                          d = {s, 1/s, 2 tan(s/2), 1/(2 tan(s/2))}
+ *
+ * What an independent derivation pins (tests/camera_reference.py: the published formulas in mpmath, held against this file by
+ * tests/test_camera_reference.py on the cases of tests/camera_cases.py): the pinhole; the radial-tangential forward model with
+ * its coefficient order, k3 != 0 included; the fixed-point form of the inverse, expressed through the forward model's own
+ * terms; the ATAN pair; reprojectPoint's truncation, border and cell.
+ * What remains a stated fact of vikit / OpenCV, which no derivation yields and the tests can only hold every implementation
+ * to: FIVE iterations; pixel, intrinsics, coefficients and result rounded to float; rtrans_factor's `r < 0.001` and cam2world's
+ * `dist_r > 0.01` (with `<` and `>` as written); `fabs(d0) > 0.0000001`; the ATAN constructor's normalisation.
  */
 #ifndef ORC_CAMERA_H_
 #define ORC_CAMERA_H_

@@ -90,6 +90,11 @@ __device__ __forceinline__ void frame_pos(const Se3& T_f_w, double p[3]) {
 // float camera matrix / distortion vector (vikit pinhole_camera.cpp): pixel, intrinsics and
 // coefficients are rounded to float first, five fixed-point iterations run in double, the result is
 // rounded to float again.
+// Pinned by an independent derivation (tests/camera_reference.py, the published formulas in mpmath; on the host, the emulated
+// library and the device: tests/test_camera_reference.py, test_camera_edges_emulated.py, test_camera_edges_gpu.py): the three
+// models, the coefficient order k1 k2 p1 p2 k3, the fixed-point inverse, truncation / border / cell of reproject_kernel.
+// Stated facts of vikit / OpenCV that the tests hold this file to but cannot derive: five iterations, the float roundings,
+// `r < 0.001` and `dist_r > 0.01` (steps of 0.03 px and 7 % of 3.8 px: quirks the product keeps), fabs(d0) > 1e-7.
 __device__ inline void cam2world(const Cam& c, double u, double v, double f[3]) {
   if (c.model == SVO_HIP_CAM_PINHOLE) {
     f[0] = (u - c.cx) / c.fx;
