@@ -741,8 +741,13 @@ int svo_hip_update_seed_batch(int S, const float* d_x, const float* d_tau2,
  *                                  setGridOccpuancy); NULL = all free
  *   detection_threshold            Config::triangMinCornerScore()
  *   d_corner_xy [n_frames][cells][2]  Corner::x, y (level-0 pixels); -1 where the cell stays empty
- *   d_corner_level / d_corner_score   Corner::level / score (score == threshold where empty)
- * A Feature is created for every cell with score > detection_threshold, in cell order (:107-110).
+ *   d_corner_level / d_corner_score   Corner::level / score; -1 / (float)detection_threshold where the cell stays
+ *                                     empty (no corner above the threshold, or an occupied cell)
+ * A cell holds a corner iff level >= 0, and a Feature is created for exactly those cells, in cell order (:107-110).
+ * The score alone does not say so: (float)detection_threshold can lie above the double it was rounded from (20.1,
+ * 0.1), and then an empty cell's score passes "score > detection_threshold".  The reference compares that way
+ * (:109) and creates a Feature at (0, 0), level 0, for every such cell; this library's consumers
+ * (svo_hip_initialize_seeds, the drop-in FastDetector::detect, the bootstrap) require level >= 0 and create none.
  */
 size_t svo_hip_fast_workspace_bytes(const svo_hip_pyr_layout* layout, int n_frames, int n_cells);
 int svo_hip_fast_detect(const svo_hip_pyr_layout* layout, const uint8_t* d_store, int n_frames,
@@ -993,7 +998,8 @@ int svo_hip_first_map(const svo_hip_camera* cam, int n_seq, int n_pts, const int
 /*
  * svo_hip_initialize_seeds.  DepthFilter::initializeSeeds after detect (depth_filter.cpp:114-132) for n_frames
  * keyframes: d_corner_xy / d_corner_level / d_corner_score [n_frames][n_cells] and detection_threshold are
- * svo_hip_fast_detect's; the cells with (double)score > detection_threshold become, in cell order, records
+ * svo_hip_fast_detect's; the cells with level >= 0 and (double)score > detection_threshold (K7's rule: no threshold turns
+ * an empty or occupied cell, level -1, into a seed, however its float score rounds) become, in cell order, records
  * 0 .. n_seeds - 1 of the frame's seed_stride (>= n_cells) records:
  *   Feature(frame, px, level) (feature.h:42-50): frame = d_frame_index[frame], px = (x, y) as f64, level, f =
  *     cam2world(px) with svo_hip_cam2world's bits, type CORNER and grad (1, 0) where d_type / d_grad are given;

@@ -202,7 +202,9 @@ __global__ void __launch_bounds__(FM_THREADS) seed_init_kernel(const SeedInitArg
   int n = 0;  // the running offset: seeds of the blocks before this one
   for (int c0 = 0; c0 < a.n_cells; c0 += FM_THREADS) {
     const int c = c0 + t;
-    const bool on = c < a.n_cells && (double)a.corner_score[in0 + (c < a.n_cells ? c : 0)] > a.detection_threshold;
+    // (an empty cell holds level -1 and (float)threshold, which can lie above the double: the level decides)
+    const size_t ci = in0 + (c < a.n_cells ? c : 0);
+    const bool on = c < a.n_cells && a.corner_level[ci] >= 0 && (double)a.corner_score[ci] > a.detection_threshold;
     const int slot = block_compact_step<FM_THREADS / 64>(on, t, s_wcnt, n);
     if (on) {
       const size_t s = out0 + slot;  // at most c: inside the frame's stride

@@ -29,18 +29,26 @@ class FastDetector:
         return self.grid_n_cols * self.grid_n_rows
 
     def occupancy_from_features(self, px: torch.Tensor) -> torch.Tensor:
-        """AbstractDetector::setExistingFeatures for px [n, m, 2] (level-0 pixels; NaN rows ignored)."""
+        """AbstractDetector::setExistingFeatures for px [n, m, 2] (level-0 pixels) -> [n, cells] u8.  Rule 5 of K10
+        (svo_hip.h): a pixel that is not finite, or whose row or column index lies outside the grid, sets no cell.  A
+        maximum, so that duplicate cells and the rows that set nothing give the same answer in any write order."""
         n, m, _ = px.shape
         occ = torch.zeros(n, self.n_cells, dtype=torch.uint8, device=px.device)
-        ok = ~torch.isnan(px[..., 0])
-        k = (px[..., 1] / self.cell_size).to(torch.int64) * self.grid_n_cols + (px[..., 0] / self.cell_size).to(torch.int64)
-        k = torch.where(ok, k, torch.zeros_like(k))
-        occ.scatter_(1, k, ok.to(torch.uint8))
+        if m == 0:
+            return occ
+        q = px / self.cell_size
+        # the index is (int)(px / cell), towards zero: inside the grid iff -1 < q < n (false for NaN; decided on the
+        # float, before a conversion that is undefined beyond the integer range)
+        ok = (q[..., 0] > -1) & (q[..., 0] < self.grid_n_cols) & (q[..., 1] > -1) & (q[..., 1] < self.grid_n_rows)
+        q = torch.where(ok[..., None], q, torch.zeros_like(q))
+        k = q[..., 1].to(torch.int64) * self.grid_n_cols + q[..., 0].to(torch.int64)
+        occ.scatter_reduce_(1, k, ok.to(torch.uint8), "amax", include_self=True)
         return occ
 
     def detect(self, store: PyramidStore, slots: torch.Tensor, detection_threshold: float = 20.0, occupancy=None):
         """-> (xy [n,cells,2] i32 level-0 px (-1 = empty cell), level [n,cells] i32, score [n,cells] f32).
-        A Feature exists where score > detection_threshold."""
+        A cell holds a corner iff level >= 0: an empty or occupied cell holds level -1 and float(detection_threshold),
+        which can lie above the double (20.1), so the score alone does not say."""
         assert slots.dtype == torch.int32 and slots.is_cuda
         n = slots.shape[0]
         dev = store.device

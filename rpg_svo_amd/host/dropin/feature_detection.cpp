@@ -74,9 +74,10 @@ void FastDetector::detect(Frame* frame, const ImgPyr& img_pyr, const double dete
   a.download(lane.stream);
   svo_hip::check(svo_hip_stream_sync(lane.stream), "svo_hip_stream_sync");
 
-  // one feature per cell whose best corner beats the threshold, in cell order (:107-110)
+  // one feature per cell whose best corner beats the threshold, in cell order (:107-110).  An empty cell holds level -1
+  // and (float)detection_threshold, which can lie above the double (20.1): the level decides, not the score alone
   for (size_t k = 0; k < n_cells; ++k)
-    if (score[k] > detection_threshold)
+    if (level[k] >= 0 && score[k] > detection_threshold)
       fts.push_back(new Feature(frame, Vector2d(xy[2 * k], xy[2 * k + 1]), level[k]));
   resetGrid();
 }

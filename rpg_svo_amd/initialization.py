@@ -190,10 +190,10 @@ class KltTracker:
         the cell holds a corner), px_cur = px_ref, f_ref [n, cells, 3]."""
         if store.n_levels <= self.params.max_level:
             raise capi.SvoHipError(f"the tracker reads pyramid levels 0..{self.params.max_level}: the store has {store.n_levels}")
-        xy, _, score = self.detector.detect(store, slots, self.min_corner_score)
+        xy, level, score = self.detector.detect(store, slots, self.min_corner_score)
         n, cells = score.shape
         self.ref_slots = slots.clone()
-        self.status = (score > self.min_corner_score).to(torch.uint8).contiguous()
+        self.status = (level >= 0).to(torch.uint8).contiguous()    # K7's rule: a cell holds a corner iff level >= 0
         self.px_ref = xy.to(torch.float32).contiguous()            # cv::Point2f(ftr->px[0], ftr->px[1])
         self.px_cur = self.px_ref.clone()
         self.f_ref = cam2world(self.cam, xy.to(torch.float64).reshape(-1, 2)).reshape(n, cells, 3)

@@ -27,6 +27,7 @@ SEED_F64 = ("px", "f", "grad")
 SEED_F32 = ("a", "b", "mu", "z_range", "sigma2")
 F64_BOUND = 1e-14
 F32_ULPS = 1
+ROUNDED_UP_THRESHOLDS = (20.1, 0.1)
 
 
 def camera(width, height):
@@ -232,17 +233,20 @@ def compare_device(got, want, discrete, f64, f32=(), what=""):
 # ---- svo_hip_initialize_seeds ------------------------------------------------------------------------------------------------
 def make_corners(seed, n_frames, n_cells, fill, cam, threshold=20.0):
     """what svo_hip_fast_detect leaves: fill = the fraction of cells with a corner (0: none, 1: every cell); empty cells hold
-    xy = -1 and score == threshold, and a few full-looking cells score exactly the threshold (not a corner: the test is >)"""
+    xy = -1, level = -1 and score == float(threshold) -- above the double for 20.1 and 0.1, and still no corner: the level
+    says so -- and a few full-looking cells (level 0) score exactly the threshold (not a corner: the test is >)"""
     rng = np.random.default_rng(seed)
     c = types.SimpleNamespace(n_frames=n_frames, n_cells=n_cells, threshold=threshold, cam=cam)
     has = rng.uniform(size=(n_frames, n_cells)) < fill
     c.xy = np.where(has[..., None], np.stack([rng.integers(0, cam.width, (n_frames, n_cells)), rng.integers(0, cam.height, (n_frames, n_cells))],
                                              axis=-1), -1).astype(np.int32)
-    c.level = np.where(has, rng.integers(0, 3, (n_frames, n_cells)), 0).astype(np.int32)
+    c.level = np.where(has, rng.integers(0, 3, (n_frames, n_cells)), -1).astype(np.int32)
     c.score = np.where(has, rng.uniform(threshold, 200.0, (n_frames, n_cells)), threshold).astype(np.float32)
     if fill and n_cells > 4:
-        c.score[:, 3] = threshold
+        at = np.float32(threshold)                      # the largest float that is not above the threshold: the threshold itself at 20.0
+        c.score[:, 3] = at if float(at) <= threshold else np.nextafter(at, np.float32(0))
         c.xy[:, 3] = (5, 6)
+        c.level[:, 3] = 0
     c.frame_index = (np.arange(n_frames) * 3 + 2).astype(np.int32)
     c.depth_mean = rng.uniform(0.5, 5.0, n_frames)
     c.depth_min = rng.uniform(0.1, 0.5, n_frames)
@@ -263,10 +267,27 @@ def seed_cases():
     zero = make_corners(9, 8, 24, 0.7, cam)
     zero.depth_mean[1], zero.depth_min[1] = 0.0, 0.0          # a failed sequence's scene depth: mu = z_range = sigma2 = inf
     out["eight_frames_zero_depth"] = (zero, 24, 5)
+    # thresholds whose float lies above the double (20.100000381 > 20.1): an empty cell's score passes "score > threshold"
+    # and its level, -1, must keep it from becoming a record
+    for threshold in ROUNDED_UP_THRESHOLDS:
+        assert float(np.float32(threshold)) > threshold
+        out[f"threshold_{threshold}"] = (make_corners(10, 3, 257, 0.5, cam, threshold=threshold), 257, 6)
     for c, stride, batch_id in out.values():
         c.expect = chk.initialize_seeds(c.cam, c.xy, c.level, c.score, c.threshold, c.frame_index, c.depth_mean, c.depth_min, batch_id, stride)
     return out
 
 
+def check_seed_rule(c, got):
+    """K7's rule, read off the inputs and not off the checker (which states the same rule as the kernel): one record per cell
+    with level >= 0 whose score beats the threshold, none for an empty cell (level -1, pixel -1), whatever its score"""
+    corner = (c.level >= 0) & (c.score.astype(np.float64) > c.threshold)
+    n = got["n_seeds"]
+    assert np.array_equal(n, corner.sum(axis=1)), (n, corner.sum(axis=1))
+    for f in range(c.n_frames):
+        assert (got["level"][f, :n[f]] >= 0).all() and (got["px"][f, :n[f]] >= 0).all(), f
+        assert np.array_equal(got["px"][f, :n[f]], c.xy[f][corner[f]].astype(np.float64)), f
+    return n
+
+
 SEED_NAMES = ("cells1", "cells255", "cells256", "cells257", "cells1040", "no_corner", "every_corner", "wide_stride", "one_cell_full",
-              "eight_frames_zero_depth")
+              "eight_frames_zero_depth") + tuple(f"threshold_{t}" for t in ROUNDED_UP_THRESHOLDS)

@@ -184,7 +184,9 @@ def initialize_seeds(cam, corner_xy, corner_level, corner_score, detection_thres
         seed = orc.seed_init(float(np.float32(depth_mean[fr])), float(np.float32(depth_min[fr])))
         n = 0
         for c in range(n_cells):   # the corners in cell order (feature_detection.cpp:107-110)
-            if not float(corner_score[fr, c]) > detection_threshold:
+            # K7's rule (svo_hip.h): a cell holds a corner iff level >= 0 -- an empty cell's float(threshold) can lie
+            # above the double.  (The reference tests the score alone and emits a feature at (0, 0) for such a cell.)
+            if corner_level[fr, c] < 0 or not float(corner_score[fr, c]) > detection_threshold:
                 continue
             px = (float(corner_xy[fr, c, 0]), float(corner_xy[fr, c, 1]))
             o["frame"][fr, n], o["level"][fr, n], o["type"][fr, n] = frame_index[fr], corner_level[fr, c], 0

@@ -332,6 +332,30 @@ def test_mock_device_standalone_seams(mock_lib):
                                 "img_align_n_tracked", "n_seeds", "n_candidates"))
 
 
+def test_mock_device_detect_creates_no_feature_for_an_empty_cell(mock_lib):
+    """The drop-in FastDetector::detect (flavour "hipmock": the one flavour on the mock device that links it; "hipm" keeps the
+    reference's detector) at Config::triangMinCornerScore() = 20.1, whose float lies above the double: the empty cells of
+    tests/fast_cases.py's case E hold a score that passes "score > threshold", and still exactly the cells with level >= 0
+    become features -- none at (-1, -1), none with a negative level."""
+    import fast_cases as fc
+    for thresh in (20.1, 20.0):
+        c = fc.case_empty(thresh, occupied=False)
+        xy, lvl, _ = (a[0] for a in c.expected())
+        has = lvl >= 0
+        assert has.sum() == 4 and c.oracle_n_features(0) == (6 if thresh == 20.1 else 4)
+        cam = synth.Camera(c.w, c.h, 80.0, 80.0, c.w / 2.0, c.h / 2.0)
+        p = pp.Pipeline("hipmock", cam, n_pyr_levels=c.n_levels, grid_size=c.cell, triang_min_corner_score=thresh)
+        try:
+            T0 = np.array([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 2.0])
+            n, _ = p.set_first_frame(c.images[0], 0.0, T0, np.full((c.h, c.w), 2.0, np.float32))
+            px, level, _ = p.last_features()
+        finally:
+            p.close()
+        assert n == len(px) == 4
+        assert (level >= 0).all() and (px >= 0).all()
+        assert np.array_equal(px, xy[has].astype(np.float64)) and np.array_equal(level, lvl[has])
+
+
 MIRROR_CODE = (
     "import sys, json, numpy as np\n"
     "sys.path.insert(0, {here!r}); sys.path.insert(0, {dropin!r})\n"

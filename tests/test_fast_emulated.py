@@ -1,5 +1,5 @@
 """Row N4 without a GPU: svo_hip_fast_detect of the host-emulated library (tests/emu_build.py: fast_detect.hip compiled
-for the CPU through tests/host/hip_emu.h) -- FAST-9 score, 3x3 non-maximum suppression, Shi-Tomasi score and the per-cell
+for the CPU through tests/host/hip_emu.h) -- FAST-10 score, 3x3 non-maximum suppression, Shi-Tomasi score and the per-cell
 maximum through 64-bit atomicMax keys -- against the oracle's FastDetector::detect: corners, levels and scores identical in
 every bit, with and without grid occupancy, on rendered frames and on a corner-dense noise image."""
 import ctypes as C
@@ -19,19 +19,28 @@ def emu():
     return build_emulated(())
 
 
-def detect(emu, imgs, n_pyr, levels, cell, occ, thresh=20.0):
-    n, h, w = imgs.shape
+def detect(emu, imgs, n_pyr, levels, cell, occ, thresh=20.0, slots=None, fast_threshold=20, n_store_slots=None, image_slots=None):
+    """svo_hip_fast_detect of the emulated library -> xy, level, score [n_frames, cells(, 2)], cols, rows.  imgs [m, h, w] go to
+    the store slots image_slots (default 0 .. m - 1) of a store of n_store_slots (default m) whose every other byte is 0xA5;
+    frame f searches slot slots[f] (default: frame f = slot f) under occ[f]."""
+    m, h, w = imgs.shape
+    n_store_slots = m if n_store_slots is None else n_store_slots
+    image_slots = range(m) if image_slots is None else image_slots
     layout = capi.pyr_layout(w, h, n_pyr)
-    store = np.zeros(capi.pyr_store_bytes(layout, n), np.uint8)
+    store = np.full(capi.pyr_store_bytes(layout, n_store_slots), 0xA5, np.uint8)
     imgs = np.ascontiguousarray(imgs)
-    assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), ptr(store), 0, n, ptr(imgs), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
+    for i, s in enumerate(image_slots):
+        assert 0 <= s < n_store_slots
+        assert emu.svo_hip_pyramid_build_tiled(C.byref(layout), ptr(store), int(s), 1, ptr(imgs[i]), C.c_longlong(h * w), w, capi.HALFSAMPLE_AUTO, 0, None) == 0
+    slots = np.arange(m, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, dtype=np.int32)
+    n = slots.size
+    assert occ is None or (occ.shape[0] == n and occ.dtype == np.uint8 and occ.flags.c_contiguous)
     cols, rows = -(-w // cell), -(-h // cell)
     nc = cols * rows
     emu.svo_hip_fast_workspace_bytes.restype = C.c_size_t
     ws = np.full(emu.svo_hip_fast_workspace_bytes(C.byref(layout), n, nc), 0xFF, np.uint8)   # (poisoned: NaN / -1 to whoever reads scratch it did not write)
-    slots = np.arange(n, dtype=np.int32)
     xy, lvl, sc = np.zeros((n, nc, 2), np.int32), np.zeros((n, nc), np.int32), np.zeros((n, nc), np.float32)
-    rc = emu.svo_hip_fast_detect(C.byref(layout), ptr(store), n, ptr(slots), levels, 20, cell, cols, rows, None if occ is None else ptr(occ),
+    rc = emu.svo_hip_fast_detect(C.byref(layout), ptr(store), n, ptr(slots), levels, fast_threshold, cell, cols, rows, None if occ is None else ptr(occ),
                                  C.c_double(thresh), ptr(xy), ptr(lvl), ptr(sc), ptr(ws), C.c_size_t(ws.size), None)
     assert rc == 0, rc
     return xy, lvl, sc, cols, rows

@@ -36,6 +36,28 @@ def test_oracle_fast_matches_reference_detector(oracle):
             assert not sel[occ.astype(bool)].any()
 
 
+def test_oracle_and_reference_report_placeholder_features_at_a_threshold_that_rounds_up(oracle):
+    """float(20.1) > 20.1: the reference's Corner(0, 0, detection_threshold, ...) of an empty or occupied cell passes its own
+    "score > detection_threshold" (feature_detection.cpp:109) and becomes a Feature at (0, 0), level 0.  The oracle counts
+    the same cells (it stays faithful); the product does not follow (a cell holds a corner iff level >= 0: DESIGN.md
+    section 4, tests/fast_cases.py case E)."""
+    import fast_cases as fc
+    from oracle import pytrack
+    if not pytrack.ref_available() and not pytrack.build_ref():
+        pytest.skip("oracle/_ref not available")
+    for thresh, placeholders in ((20.0, False), (20.1, True), (20.3, False), (0.1, True)):
+        c = fc.case_empty(thresh)
+        xy, lvl, sc = (a[0] for a in c.expected())
+        cam = synth.Camera(c.w, c.h, 100.0, 100.0, c.w / 2.0, c.h / 2.0)
+        px_ref, lvl_ref = pytrack.ref_fast_detect(c.pyramid(0), cam, c.n_levels, c.cell, c.occ[0], thresh)
+        has = lvl >= 0
+        assert has.sum() == 3 and c.oracle_n_features(0) == len(px_ref) == (c.n_cells if placeholders else 3)
+        sel = sc.astype(np.float64) > thresh                              # the reference's test, on the oracle's scores
+        assert sel.sum() == len(px_ref) and np.array_equal(sel, has | placeholders)
+        assert np.array_equal(px_ref, np.where(has[:, None], xy, 0)[sel].astype(np.float64))
+        assert np.array_equal(lvl_ref, np.where(has, lvl, 0)[sel])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,f,levels,cell", [(752, 480, 315.5, 3, 30), (640, 480, 400.0, 4, 25), (1280, 960, 800.0, 5, 30)])
 def test_fast_detect_bit_exact(oracle, gpu_device, w, h, f, levels, cell):

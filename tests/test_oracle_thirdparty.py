@@ -58,24 +58,9 @@ def test_compute_tau_is_the_law_of_sines(oracle):
         assert np.isclose(orc.compute_tau(T, f, z, ang), z_plus - z, rtol=1e-10, atol=1e-14)
 
 
-RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
-
-
-def _is_corner(img, x, y, b):
-    p = int(img[y, x])
-    ring = [int(img[y + dy, x + dx]) for dx, dy in RING]
-    for sign in (1, -1):
-        flags = [(v > p + b) if sign == 1 else (v < p - b) for v in ring]
-        run = best = 0
-        for f in flags + flags:  # circular
-            run = run + 1 if f else 0
-            best = max(best, run)
-        if best >= 10:
-            return True
-    return False
-
-
 def test_fast10_score_nonmax_and_shi_tomasi_against_brute_force(oracle):
+    """(the brute force lives in tests/fast_reference.py, which extends it to the whole of FastDetector::detect)"""
+    import fast_reference as fr
     rng = np.random.default_rng(3)
     h, w = 40, 56
     img = rng.integers(0, 256, size=(h, w)).astype(np.uint8)
@@ -84,34 +69,16 @@ def test_fast10_score_nonmax_and_shi_tomasi_against_brute_force(oracle):
     # cell size 1: every pixel is its own grid cell, so the grid output IS the list of surviving corners
     xy, lvl, sc, n = pytrack.fast_detect_grid(pyr, 1, 1, w, h, None, 20, 0.0)
     got = {(int(x), int(y)): float(s) for (x, y), s, l in zip(xy, sc, lvl) if l >= 0}
-    corners = {}
-    for y in range(3, h - 3):
-        for x in range(3, w - 3):
-            if _is_corner(img, x, y, 20):
-                lo, hi = 20, 255   # fast_corner_score_10: largest threshold that still passes
-                t = (lo + hi) // 2
-                while True:
-                    if _is_corner(img, x, y, t):
-                        lo = t
-                    else:
-                        hi = t
-                    if lo == hi - 1 or lo == hi:
-                        break
-                    t = (lo + hi) // 2
-                corners[(x, y)] = lo
+    S = fr.fast_scores(img, 20)   # fast_corner_score_10: largest threshold that still passes, -1 where no corner
+    corners = {(int(x), int(y)): int(S[y, x]) for y, x in zip(*np.nonzero(S >= 0))}
     assert len(corners) > 30
+    assert all(3 <= x < w - 3 and 3 <= y < h - 3 and fr.is_corner(img, x, y, s) and not fr.is_corner(img, x, y, s + 1) for (x, y), s in corners.items())
     expect = {}
-    I = img.astype(np.float64)
+    keep = fr.nonmax_3x3(S)       # fast_nonmax_3x3: a neighbouring corner with score >= own suppresses
     for (x, y), s in corners.items():
-        if any(corners.get((x + dx, y + dy), -1) >= s for dx in (-1, 0, 1) for dy in (-1, 0, 1) if (dx, dy) != (0, 0)):
-            continue  # fast_nonmax_3x3: a neighbouring corner with score >= own suppresses
-        if x - 4 < 1 or x + 4 >= w - 1 or y - 4 < 1 or y + 4 >= h - 1:
-            continue  # vk::shiTomasiScore returns 0 next to the border: never above the threshold
-        ys, xs = slice(y - 4, y + 4), slice(x - 4, x + 4)
-        dx = I[ys, x - 3:x + 5] - I[ys, x - 5:x + 3]
-        dy = I[y - 3:y + 5, xs] - I[y - 5:y + 3, xs]
-        dxx, dyy, dxy = (dx * dx).sum() / 128, (dy * dy).sum() / 128, (dx * dy).sum() / 128
-        lam = 0.5 * (dxx + dyy - math.sqrt((dxx + dyy) ** 2 - 4 * (dxx * dyy - dxy * dxy)))
+        if not keep[y, x]:
+            continue
+        lam = fr.shi_tomasi(img, x, y)   # vk::shiTomasiScore returns 0 next to the border: never above the threshold
         if lam > 0.0:
             expect[(x, y)] = lam
     assert set(got) == set(expect)
