@@ -86,11 +86,8 @@ __device__ __forceinline__ void align2d_wave(const uint8_t* __restrict__ img, in
   {
     const float part[8] = {gx2 * gx2, gx2 * gy2, gy2 * gy2, gx2, gy2, 0.f, 0.f, 0.f};
     const float tot = svo_dev::wave_reduce8(part, lane);  // lanes 8g .. 8g+7 hold the total of part[g]
-    const float sxx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 0));
-    const float sxy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 8));
-    const float syy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 16));
-    const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 24));
-    const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 32));
+    const float sxx = svo_dev::readlane_f32(tot, 0), sxy = svo_dev::readlane_f32(tot, 8), syy = svo_dev::readlane_f32(tot, 16);
+    const float sx = svo_dev::readlane_f32(tot, 24), sy = svo_dev::readlane_f32(tot, 32);
     H[0] = 0.25f * sxx;
     H[1] = H[3] = 0.25f * sxy;
     H[4] = 0.25f * syy;

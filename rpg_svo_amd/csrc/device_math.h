@@ -425,6 +425,18 @@ __device__ __forceinline__ double readlane_f64(double v) {
   const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), SRC);
   return __longlong_as_double(((unsigned long long)hi << 32) | lo);
 }
+// lane `src` (wave-uniform) of a float, as a wave-uniform value
+__device__ __forceinline__ float readlane_f32(float v, int src) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+// 1 / z as v_rcp_f64 + two Newton steps: a third of the IEEE division sequence, for the tolerance-mode kernels (K1: the
+// agreement with the reference's translation unit is the same to six digits either way, profiles/r06ah_*)
+__device__ __forceinline__ double fast_rcp(double z) {
+  double r = __builtin_amdgcn_rcp(z);
+  r = fma(fma(-z, r, 1.0), r, r);
+  r = fma(fma(-z, r, 1.0), r, r);
+  return r;
+}
 #endif
 
 // index into the packed upper triangle of a symmetric 6x6 (row-major, i<=j)

@@ -91,7 +91,7 @@ __device__ __forceinline__ void wave_sums(const float part[NV], int lane, float 
   for (int k = 0; k < 8; ++k) v[k] = k < NV ? part[k] : 0.0f;
   const float t = wave_reduce8(v, lane);  // lanes 8g .. 8g+7 hold the total of v[g]
 #pragma unroll
-  for (int k = 0; k < NV; ++k) out[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 8 * k));
+  for (int k = 0; k < NV; ++k) out[k] = readlane_f32(t, 8 * k);
 }
 
 // floor(t) as an int when -KLT_WIN <= floor(t) < size (the window's corner is close enough to the level), else false

@@ -53,19 +53,13 @@ constexpr int PW_MINW = 4;  // waves per SIMD asked of the register allocator (<
 constexpr double SVO_EPS = 0.0000000001;  // svo/include/svo/global.h:77
 
 
-// A wave-uniform value computed by the VALU lives in a VGPR pair; reading it back through
-// v_readfirstlane moves it to SGPRs.  The pose (R, t, quaternion, rollback copy) is 38 doubles:
-// kept in VGPRs it would cost 76 registers per lane next to the resident observations.
-__device__ __forceinline__ double uni(double v) {
-  const uint32_t l = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo32(v));
-  const uint32_t h = (uint32_t)__builtin_amdgcn_readfirstlane((int)hi32(v));
-  return mk_f64(l, h);
-}
+// The pose (R, t, quaternion, rollback copy) is 38 doubles: kept in VGPRs it would cost 76 registers per lane next to
+// the resident observations; uniform_f64 (device_math.h) moves them to SGPRs.
 __device__ __forceinline__ void uni_se3(Se3& T) {
 #pragma unroll
-  for (int k = 0; k < 4; ++k) T.q[k] = uni(T.q[k]);
+  for (int k = 0; k < 4; ++k) T.q[k] = uniform_f64(T.q[k]);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) T.t[k] = uni(T.t[k]);
+  for (int k = 0; k < 3; ++k) T.t[k] = uniform_f64(T.t[k]);
 }
 
 
@@ -99,12 +93,6 @@ __device__ __forceinline__ double wave_reduce32_f64(const double v[32], int lane
   return w;
 }
 
-__device__ __forceinline__ double fast_rcp(double z) {
-  double r = __builtin_amdgcn_rcp(z);
-  r = fma(fma(-z, r, 1.0), r, r);
-  r = fma(fma(-z, r, 1.0), r, r);
-  return r;
-}
 // sqrt for x >= 0 (v_rsq_f64 seed + two coupled Newton steps), 0 for x == 0
 __device__ __forceinline__ double fast_sqrt(double x) {
   const double r = __builtin_amdgcn_rsq(x);
@@ -357,7 +345,7 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   double R[9];
   quat_to_R(T.q, R);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = uni(R[k]);
+  for (int k = 0; k < 9; ++k) R[k] = uniform_f64(R[k]);
 
   // ---- error scale (:45-60) and the median of chi2_vec_init (same residuals as iteration 0) ----
   double estimated_scale, med_init;
@@ -487,7 +475,7 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     }
     quat_to_R(T.q, R);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = uni(R[k]);
+    for (int k = 0; k < 9; ++k) R[k] = uniform_f64(R[k]);
     last = last || iter + 1 == a.n_iter;
     if (last) {
       // covariance (:124-126): (A f^2)^-1 = A^-1 / f^2 with the A of the last evaluated iteration,

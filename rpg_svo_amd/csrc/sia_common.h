@@ -139,15 +139,6 @@ __device__ __forceinline__ void cut_row5_plain(const uint32_t d[3], uint32_t bo,
   out[4] = (float)(hi & 0xffu);
 }
 
-// 1 / z as v_rcp_f64 + two Newton steps (the IEEE division sequence is three times as long; K1 is a tolerance-mode kernel
-// and its agreement with the reference's translation unit is the same to six digits either way: profiles/r06ah_*)
-__device__ __forceinline__ double sia_rcp(double z) {
-  double r = __builtin_amdgcn_rcp(z);
-  r = fma(fma(-z, r, 1.0), r, r);
-  r = fma(fma(-z, r, 1.0), r, r);
-  return r;
-}
-
 // ---- window cache (template parameter WC) --------------------------------------------------------------
 // The 5x5 window of the current image moves by a fraction of a pixel per Gauss-Newton iteration,
 // yet re-fetching it every iteration misses L2 (128 resident problems per XCD x ~64 KB of touched
@@ -179,15 +170,6 @@ __device__ __forceinline__ void cut_row5(uint32_t a, uint32_t b, uint32_t c, int
   out[3] = (float)(lo >> 24);
   out[4] = (float)(hi & 0xffu);
 }
-
-// a wave-uniform value read back through v_readfirstlane: its dwords stay in SGPRs instead of VGPRs
-__device__ __forceinline__ double sia_uni(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
 
 __device__ __forceinline__ int sym6_rt(int i, int j) {
   const int a = i < j ? i : j, b = i < j ? j : i;
@@ -232,6 +214,16 @@ __device__ __forceinline__ sia_f2 sia_bilerp2(sia_f2 wtl, sia_f2 wtr, sia_f2 wbl
   return __builtin_elementwise_fma(wbr, br, __builtin_elementwise_fma(wbl, bl, __builtin_elementwise_fma(wtr, tr, wtl * tl)));
 }
 
+// The bilinear weights.  The reference forms these products in double and rounds to float (:118-121, :200-203).  u >= 3
+// here, so su and sv are multiples of 2^-22: 1-su and 1-sv are exact in f32, and the f32 product of two f32 values is
+// the correctly rounded exact product, like the rounded double product -- bit-identical.
+__device__ __forceinline__ void sia_weights(float su, float sv, float& wtl, float& wtr, float& wbl, float& wbr) {
+  wtl = (1.f - su) * (1.f - sv);
+  wtr = su * (1.f - sv);
+  wbl = (1.f - su) * sv;
+  wbr = su * sv;
+}
+
 // bytes [bo, bo+6] of a 12-byte run as the column pairs (0,2) (1,3) (2,4) (3,5) (4,5) (5,6) the packed samples read
 __device__ __forceinline__ void sia_cut_row7_pairs(const uint32_t d[3], uint32_t bo, sia_f2 p[6]) {
   float w[7];
@@ -271,13 +263,8 @@ __device__ __forceinline__ float4 sia_f4(sia_f2 a, sia_f2 b) { return make_float
 template <typename STORE>
 __device__ __forceinline__ void sia_ref_tile_packed(const uint32_t rw[7][3], uint32_t rbo, float su, float sv, STORE&& store,
                                                     float& Sxx, float& Sxy, float& Syy) {
-  // The reference forms these products in double and rounds to float (:118-121).  u >= 3 here, so su
-  // and sv are multiples of 2^-22: 1-su and 1-sv are exact in f32, and the f32 product of two f32
-  // values is the correctly rounded exact product, like the rounded double product -- bit-identical.
-  const float wtl = (1.f - su) * (1.f - sv);
-  const float wtr = su * (1.f - sv);
-  const float wbl = (1.f - su) * sv;
-  const float wbr = su * sv;
+  float wtl, wtr, wbl, wbr;
+  sia_weights(su, sv, wtl, wtr, wbl, wbr);
   const sia_f2 vtl = sia_f2{wtl, wtl}, vtr = sia_f2{wtr, wtr}, vbl = sia_f2{wbl, wbl}, vbr = sia_f2{wbr, wbr};
   const sia_f2 z2 = sia_f2{0.f, 0.f};
   float sxx = 0.f, sxy = 0.f, syy = 0.f;
@@ -331,6 +318,216 @@ __device__ __forceinline__ void sia_ref_tile_packed(const uint32_t rw[7][3], uin
   Sxx = 0.25f * sxx;
   Sxy = 0.25f * sxy;
   Syy = 0.25f * syy;
+}
+
+// ---- what both kernels do the same way, once ---------------------------------------------------------------------------
+// sparse_img_align.cpp:47-51: nothing to track, pose untouched (one lane of the frame writes)
+__device__ __forceinline__ void sia_untracked(const SiaArgs& a, int b) {
+  for (int k = 0; k < 12; ++k) a.T_out[12 * b + k] = a.T_in[12 * b + k];
+  if (a.H_out)
+    for (int k = 0; k < 36; ++k) a.H_out[36 * b + k] = 0.0;
+  a.n_tracked[b] = 0;
+  if (a.iters)
+    for (int k = 0; k < SVO_HIP_MAX_LEVELS; ++k) a.iters[SVO_HIP_MAX_LEVELS * b + k] = 0;
+  if (a.chi2) a.chi2[b] = 1e10;
+  if (a.status) a.status[b] = 0;
+}
+
+// pyramid geometry per level in LDS (copied from the kernel arguments so that the level loop can index it dynamically;
+// the six-line copy loop stays in each kernel: as a function it cost sia_kernel<256, true, false, 1> a VGPR, profiles/r10a_*)
+struct SiaLevels {
+  long long lo[SVO_HIP_MAX_LEVELS];
+  int lw[SVO_HIP_MAX_LEVELS], lh[SVO_HIP_MAX_LEVELS], lp[SVO_HIP_MAX_LEVELS];
+};
+
+// The model a frame starts from: T_in (rotation row-major, then translation) as the unit quaternion Sophus stores, and the
+// rotation matrix of that quaternion (what every later update produces).  Every lane computes the same values.
+__device__ __forceinline__ void sia_model_init(const double* T, double q[4], double R[9], double tr[3]) {
+  for (int k = 0; k < 9; ++k) R[k] = T[k];
+  for (int k = 0; k < 3; ++k) tr[k] = T[9 + k];
+  quat_from_R(R, q);
+  quat_to_R(q, R);
+}
+
+// the camera of a distorted model from the kernel's parameter block
+__device__ __forceinline__ Cam sia_cam(const svo_hip_sia_params& P) {
+  Cam cm;
+  cm.fx = P.fx; cm.fy = P.fy; cm.cx = P.cx; cm.cy = P.cy;
+  cm.width = 0; cm.height = 0;
+  cm.model = P.cam_model;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) cm.d[k] = P.d[k];
+  return cm;
+}
+// cam_->world2cam(project2d(T * xyz)) (:183) at level 0, one reciprocal (fast_rcp: the IEEE division sequence sits on
+// the critical path of every iteration).  DIST: a distorted model (radial-tangential pinhole or ATAN); the undistorted
+// pinhole keeps its own instantiation so that its inner loop carries no model dispatch.
+template <bool DIST>
+__device__ __forceinline__ void sia_project(const svo_hip_sia_params& P, const double R[9], const double tr[3], double X, double Y,
+                                            double Z, double& pu, double& pv) {
+  const double xc = R[0] * X + R[1] * Y + R[2] * Z + tr[0];
+  const double yc = R[3] * X + R[4] * Y + R[5] * Z + tr[1];
+  const double zc = R[6] * X + R[7] * Y + R[8] * Z + tr[2];
+  const double izc = fast_rcp(zc);
+  if (DIST) {
+    const Cam cm = sia_cam(P);
+    const double uvn[2] = {xc * izc, yc * izc};
+    double pxd[2];
+    world2cam_uv(cm, uvn, pxd);
+    pu = pxd[0];
+    pv = pxd[1];
+  } else {
+    pu = P.fx * (xc * izc) + P.cx;
+    pv = P.fy * (yc * izc) + P.cy;
+  }
+}
+// the 4 x 4 patch and its bilinear neighbours 3 px inside the level (fu, fv: floored position; NaN / huge coordinates fail
+// the comparisons like the reference's int tests do)
+__device__ __forceinline__ bool sia_inside3(float fu, float fv, int cols, int rows) {
+  return fu - 3.f >= 0.f && fv - 3.f >= 0.f && fu + 3.f < (float)cols && fv + 3.f < (float)rows;
+}
+
+// The window cache of one patch (see above): rows = 7 runs of 12 bytes of the current level, columns [u0, u0+11], rows
+// [v0, v0+6]; v0 = -100000 while it is empty.  (Free functions over the caller's own registers: as members of a struct
+// they moved sia_kernel's register allocation, profiles/r10a_*.)  ROWS = 1: an instantiation without the cache.
+// sia_wave_kernel calls the two below; sia_kernel keeps the same lines written out in its iteration (with the calls it
+// measured slower, r10a section 4).
+// r0 (0..2), bo (0..7): the first cached row / byte of the 5 x 5 window around (u_i, v_i); fetched again when the window
+// has moved out of the cache
+template <int ROWS>
+__device__ __forceinline__ void sia_wc_seek(uint32_t (&rows)[ROWS][3], int& u0, int& v0, const uint8_t* cur_img, int pitch,
+                                            int u_i, int v_i, int& r0, int& bo) {
+  r0 = (v_i - 2) - v0;
+  bo = (u_i - 2) - u0;
+  if (!(r0 >= 0 && r0 <= 2 && bo >= 0 && bo <= 7)) {
+    v0 = v_i - 3;
+    u0 = run_start(u_i - 3, 7);
+    load_window12<ROWS>(cur_img, pitch, u0, v0, rows);
+    r0 = 1;
+    bo = (u_i - 2) - u0;
+  }
+}
+// window row r (0..4) as five floats; k0 / k1 / kup: the lanes with r0 == 0 / r0 == 1 / bo >= 4
+template <int ROWS>
+__device__ __forceinline__ void sia_wc_row(const uint32_t (&rows)[ROWS][3], int r, uint64_t k0, uint64_t k1, uint64_t kup, int bo,
+                                           float out[5]) {
+  constexpr int S = ROWS == 7 ? 1 : 0;  // keeps the indices in range when the cache is compiled out
+  const uint32_t d0 = sel_e64(k0, rows[r * S][0], sel_e64(k1, rows[(r + 1) * S][0], rows[(r + 2) * S][0]));
+  const uint32_t d1 = sel_e64(k0, rows[r * S][1], sel_e64(k1, rows[(r + 1) * S][1], rows[(r + 2) * S][1]));
+  const uint32_t d2 = sel_e64(k0, rows[r * S][2], sel_e64(k1, rows[(r + 1) * S][2], rows[(r + 2) * S][2]));
+  cut_row5(d0, d1, d2, bo, kup, out);
+}
+
+// The 6 x 6 tile of interpolated reference samples without its corners <-> the eight float4 of its LDS slot (slot(k): a
+// reference to the k-th float4), in plain order
+//   q0 = r0 c1..4 | q1 = r1 c0..3 | q2 = r1 c4,5 r2 c0,1 | q3 = r2 c2..5
+//   q4 = r3 c0..3 | q5 = r3 c4,5 r4 c0,1 | q6 = r4 c2..5 | q7 = r5 c1..4
+// and in the order the packed pixel loop pairs the columns (sia_ref_tile_packed).
+template <typename SLOT>
+__device__ __forceinline__ void sia_tile_store(const float Bt[6][6], SLOT&& slot) {
+  slot(0) = make_float4(Bt[0][1], Bt[0][2], Bt[0][3], Bt[0][4]);
+  slot(1) = make_float4(Bt[1][0], Bt[1][1], Bt[1][2], Bt[1][3]);
+  slot(2) = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][1]);
+  slot(3) = make_float4(Bt[2][2], Bt[2][3], Bt[2][4], Bt[2][5]);
+  slot(4) = make_float4(Bt[3][0], Bt[3][1], Bt[3][2], Bt[3][3]);
+  slot(5) = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][1]);
+  slot(6) = make_float4(Bt[4][2], Bt[4][3], Bt[4][4], Bt[4][5]);
+  slot(7) = make_float4(Bt[5][1], Bt[5][2], Bt[5][3], Bt[5][4]);
+}
+template <typename SLOT>
+__device__ __forceinline__ void sia_tile_store_packed(const float Bt[6][6], SLOT&& slot) {
+  slot(0) = make_float4(Bt[0][1], Bt[0][3], Bt[0][2], Bt[0][4]);
+  slot(1) = make_float4(Bt[1][0], Bt[1][2], Bt[1][1], Bt[1][3]);
+  slot(2) = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][2]);
+  slot(3) = make_float4(Bt[2][1], Bt[2][3], Bt[2][4], Bt[2][5]);
+  slot(4) = make_float4(Bt[3][0], Bt[3][2], Bt[3][1], Bt[3][3]);
+  slot(5) = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][2]);
+  slot(6) = make_float4(Bt[4][1], Bt[4][3], Bt[4][4], Bt[4][5]);
+  slot(7) = make_float4(Bt[5][1], Bt[5][3], Bt[5][2], Bt[5][4]);
+}
+// (plain order; the four corners come back as zero)
+template <typename SLOT>
+__device__ __forceinline__ void sia_tile_load(SLOT&& slot, float Bt[6][6]) {
+  const float4 q0 = slot(0), q1 = slot(1), q2 = slot(2), q3 = slot(3);
+  const float4 q4 = slot(4), q5 = slot(5), q6 = slot(6), q7 = slot(7);
+  Bt[0][0] = Bt[0][5] = Bt[5][0] = Bt[5][5] = 0.f;
+  Bt[0][1] = q0.x; Bt[0][2] = q0.y; Bt[0][3] = q0.z; Bt[0][4] = q0.w;
+  Bt[1][0] = q1.x; Bt[1][1] = q1.y; Bt[1][2] = q1.z; Bt[1][3] = q1.w;
+  Bt[1][4] = q2.x; Bt[1][5] = q2.y; Bt[2][0] = q2.z; Bt[2][1] = q2.w;
+  Bt[2][2] = q3.x; Bt[2][3] = q3.y; Bt[2][4] = q3.z; Bt[2][5] = q3.w;
+  Bt[3][0] = q4.x; Bt[3][1] = q4.y; Bt[3][2] = q4.z; Bt[3][3] = q4.w;
+  Bt[3][4] = q5.x; Bt[3][5] = q5.y; Bt[4][0] = q5.z; Bt[4][1] = q5.w;
+  Bt[4][2] = q6.x; Bt[4][3] = q6.y; Bt[4][4] = q6.z; Bt[4][5] = q6.w;
+  Bt[5][1] = q7.x; Bt[5][2] = q7.y; Bt[5][3] = q7.z; Bt[5][4] = q7.w;
+}
+
+// a = fl * jac.row(0), b = fl * jac.row(1) of Frame::jacobian_xyz2uv (frame.h:116-138) from the normalised coordinates
+// (x/z, y/z, 1/z) of xyz_ref.  The callers hand over opaque copies of zi / xn / yn (an empty asm): otherwise these
+// products, all invariant in the iteration loop, are hoisted out of it and stay live across it.
+template <typename T>
+__device__ __forceinline__ void sia_jac_rows(T zi, T xn, T yn, T fl, T ja[6], T jb[6]) {
+  const T one = 1, zero = 0;
+  ja[0] = -zi * fl; ja[1] = zero; ja[2] = xn * zi * fl; ja[3] = xn * yn * fl; ja[4] = -(one + xn * xn) * fl; ja[5] = yn * fl;
+  jb[0] = zero; jb[1] = -zi * fl; jb[2] = yn * zi * fl; jb[3] = (one + yn * yn) * fl; jb[4] = -xn * yn * fl; jb[5] = -xn * fl;
+}
+// What a patch adds to an evaluation's eight sums: Jres -= J res with J = dx a + dy b (gx / gy: the patch's sums of res dx and
+// res dy without the central difference's factor 0.5), chi2 (c2), n_meas.  m: the patch lies inside the current image;
+// gmask: 0 while its Jacobian columns are zero at this level.  (sia_kernel keeps these lines written out, as the window
+// cache above; tests/host/k1_level_arith_main.cpp holds this function to that formula bit for bit.)
+template <typename T>
+__device__ __forceinline__ void sia_jres_partials(T zi, T xn, T yn, T fl, T gmask, bool m, T gx, T gy, float c2, T part[8]) {
+  const T gsc = (T)0.5 * fl * gmask;
+  const T gxf = m ? gx * gsc : (T)0, gyf = m ? gy * gsc : (T)0;
+  part[0] = zi * gxf;
+  part[1] = zi * gyf;
+  part[2] = -zi * (xn * gxf + yn * gyf);
+  part[3] = -(xn * yn * gxf + ((T)1 + yn * yn) * gyf);
+  part[4] = ((T)1 + xn * xn) * gxf + xn * yn * gyf;
+  part[5] = xn * gyf - yn * gxf;
+  part[6] = (T)c2;
+  part[7] = m ? (T)16 : (T)0;
+}
+
+// H^-1 of the packed upper triangle H by Gauss-Jordan on a 6 x 6 tile held one element per lane (36 lanes of one wave;
+// every lane of the wave calls), LDS (A: scratch, Hinv: the result, row-major) as the row / column exchange: a few
+// registers instead of the ~90 a register LDL^T keeps live.  Same-wave LDS traffic: DS instructions of one wave execute
+// in order; the wavefront-scope fences stop the compiler from moving accesses across the exchanges.  A zero pivot
+// contributes nothing, like the D^-1 step of Eigen's LDLT::solve.
+// (fast_rcp, not 1.0 / p: six dependent divisions per rebuild of H^-1 -- K1 1.220 -> 1.207 ms together with the patch's
+// normalised coordinates, profiles/r06ah_*)
+__device__ __forceinline__ void sia_gauss_jordan6(const double* H, double* A, double* Hinv, int lane) {
+  const int gi = lane / 6, gj = lane - 6 * gi;
+  if (lane < 36) {
+    A[lane] = H[sym6_rt(gi, gj)];
+    Hinv[lane] = (gi == gj) ? 1.0 : 0.0;
+  }
+  for (int k = 0; k < 6; ++k) {
+    SVO_WAVE_LDS_FENCE();
+    if (lane < 36) {
+      const double p = A[k * 6 + k];
+      const double aik = A[gi * 6 + k];
+      const double akj = A[k * 6 + gj];
+      const double bkj = Hinv[k * 6 + gj];
+      const double aij = A[lane];
+      const double bij = Hinv[lane];
+      const double ip = (fabs(p) > 2.2250738585072014e-308) ? fast_rcp(p) : 0.0;
+      const double na = (gi == k) ? akj * ip : aij - aik * (akj * ip);
+      const double nb = (gi == k) ? bkj * ip : bij - aik * (bkj * ip);
+      SVO_LANES_LDS_FENCE();
+      A[lane] = na;
+      Hinv[lane] = nb;
+    }
+  }
+}
+// x_ = H_.ldlt().solve(Jres_) (:247), here x = H^-1 Jres from the wave-uniform totals b0..b5: lane i (< 6) holds x_i
+__device__ __forceinline__ double sia_solve_rows(const double* Hinv, double b0, double b1, double b2, double b3, double b4, double b5,
+                                                 int lane) {
+  const double* row = &Hinv[6 * (lane < 6 ? lane : 0)];
+  return row[0] * b0 + row[1] * b1 + row[2] * b2 + row[3] * b3 + row[4] * b4 + row[5] * b5;
+}
+// vk::norm_max(x_)
+__device__ __forceinline__ double sia_norm_max6(double x0, double x1, double x2, double x3, double x4, double x5) {
+  return fmax(fmax(fmax(fabs(x0), fabs(x1)), fmax(fabs(x2), fabs(x3))), fmax(fabs(x4), fabs(x5)));
 }
 
 // sparse_align_wave.hip

@@ -26,6 +26,10 @@
 //     partials from LDS, multiplies by the cached H^-1, applies the stop / rollback
 //     rules and publishes the new pose through LDS; the others wait at a barrier.
 //
+// What the wave-per-frame kernel (sparse_align_wave.hip) does the same way -- the projection, the bilinear weights, the window
+// cache, the Jacobian rows and the eight partials of a patch, the Gauss-Jordan inverse, x = H^-1 Jres -- is defined once in
+// sia_common.h; the pixel loops below stay in the kernel (as functions they cost registers: DESIGN.md, K1).
+//
 // Numerics: pixel math in f32 (like the reference); projection, the Jacobian rows, the Jres / H partials and their
 // reductions, the solve and the pose in f64 (like the reference).  The 16 per-pixel products of a patch and their sums
 // are f32 (the reference forms them in f64): exact products of 24-bit factors, summed 16 at a time.  Sums are tree-
@@ -108,19 +112,13 @@ struct SiaLds {
   int chg[2][MAX_WAVES];          // per wave: some patch entered or left the current image (same buffering)
   int xfail;                      // ... some lane of the workgroup gave up waiting for a sibling part
   sia_acc Hpart[MAX_WAVES][24];   // per-wave partials of H (21 used)
-  long long lo[SVO_HIP_MAX_LEVELS];  // pyramid geometry per level (copied from the kernel
-  int lw[SVO_HIP_MAX_LEVELS];        // arguments so the level loop can index it dynamically)
-  int lh[SVO_HIP_MAX_LEVELS];
-  int lp[SVO_HIP_MAX_LEVELS];
+  SiaLevels lv;
 };
 __shared__ SiaLds g_s;
 
 
-// H = sum of the per-wave partials, then H^-1 by Gauss-Jordan on a 6x6 tile held one
-// element per lane (36 lanes), LDS as the row/column exchange.  Wave 0 only; runs
-// once per level (or when the set of patches inside the current image changes).
-// Same-wave LDS traffic: DS instructions of one wave execute in order; the
-// wavefront-scope fences stop the compiler from moving accesses across the exchanges.
+// H = sum of the per-wave partials, then H^-1 (sia_gauss_jordan6).  Wave 0 only; runs once per level (or when the set of
+// patches inside the current image changes).
 // PARTS > 1: the workgroup's sums are one part of the frame's; the parts exchange them (xh: the frame's H chunks of this
 // exchange's buffer half, [PARTS][SIA_XH_SLOTS]) and every part adds them up in the same order.
 template <int PARTS>
@@ -157,32 +155,64 @@ __device__ __forceinline__ void sia_rebuild_hinv(int lane, int nw, [[maybe_unuse
     g_s.H[lane] = v;
   }
   SVO_WAVE_LDS_FENCE();
-  const int gi = lane / 6, gj = lane - 6 * gi;
-  if (lane < 36) {
-    g_s.A[lane] = g_s.H[sym6_rt(gi, gj)];
-    g_s.Hinv[lane] = (gi == gj) ? 1.0 : 0.0;
-  }
-  for (int k = 0; k < 6; ++k) {
-    SVO_WAVE_LDS_FENCE();
-    if (lane < 36) {
-      const double p = g_s.A[k * 6 + k];
-      const double aik = g_s.A[gi * 6 + k];
-      const double akj = g_s.A[k * 6 + gj];
-      const double bkj = g_s.Hinv[k * 6 + gj];
-      const double aij = g_s.A[lane];
-      const double bij = g_s.Hinv[lane];
-      // a zero pivot contributes nothing, like the D^-1 step of Eigen's LDLT::solve
-      // (sia_rcp, not 1.0 / p: six dependent divisions per rebuild of H^-1 -- K1 1.220 -> 1.207 ms together with the patch's
-      // normalised coordinates, profiles/r06ah_*)
-      const double ip = (fabs(p) > 2.2250738585072014e-308) ? sia_rcp(p) : 0.0;
-      const double na = (gi == k) ? akj * ip : aij - aik * (akj * ip);
-      const double nb = (gi == k) ? bkj * ip : bij - aik * (bkj * ip);
-      SVO_LANES_LDS_FENCE();
-      g_s.A[lane] = na;
-      g_s.Hinv[lane] = nb;
-    }
+  sia_gauss_jordan6(g_s.H, g_s.A, g_s.Hinv, lane);
+}
+
+// The lane's part of an H rebuild: H_p of its patch (S = 0, exact zeros in every entry, for a patch outside the current
+// image), summed over the wave into g_s.Hpart[wave].
+__device__ __forceinline__ void sia_hessian_partials(sia_acc zi, sia_acc xn, sia_acc yn, sia_acc fl, bool m, sia_pix Sxx, sia_pix Sxy,
+                                                     sia_pix Syy, int lane, int wave) {
+  const sia_acc zero = 0;
+  sia_acc ja[6], jb[6];
+  sia_jac_rows<sia_acc>(zi, xn, yn, fl, ja, jb);
+  const sia_acc sxx = m ? (sia_acc)Sxx : zero, sxy = m ? (sia_acc)Sxy : zero, syy = m ? (sia_acc)Syy : zero;
+  sia_acc hp[24];
+  sia_patch_hessian<sia_acc>(ja, jb, sxx, sxy, syy, hp);
+  hp[21] = hp[22] = hp[23] = zero;
+#pragma unroll
+  for (int g = 0; g < 3; ++g) {
+    const sia_acc tot = wave_reduce8(hp + 8 * g, lane);
+    if ((lane & 7) == 0) g_s.Hpart[wave][8 * g + (lane >> 3)] = tot;
   }
 }
+
+// the frame's pose and H_ of its last evaluated iteration (one lane)
+__device__ __forceinline__ void sia_write_pose_and_H(const SiaArgs& a, int b, const double R[9], const double tr[3]) {
+  for (int k = 0; k < 9; ++k) a.T_out[12 * b + k] = R[k];
+  for (int k = 0; k < 3; ++k) a.T_out[12 * b + 9 + k] = tr[k];
+  if (a.H_out)
+    for (int i = 0; i < 6; ++i)
+      for (int j = 0; j < 6; ++j) a.H_out[36 * b + i * 6 + j] = g_s.H[sym6_rt(i, j)];
+}
+
+#ifndef SVO_HOST_MATH_TEST
+// PARTS > 1, the sum exchange of an iteration: lane k < 9 of every wave gets the FRAME's sum k of g_s.part[buf] (k = 8:
+// "changed" anywhere).  Every wave takes part (no second barrier): lane = (part xp, sum xk); the workgroup's own sums come
+// from LDS, one wave (publish) stores them, the other parts' are polled.  (One polling wave per workgroup that hands the
+// sums to the others through LDS behind a second barrier measured the same: 0.0938 against 0.0949 ms, profiles/r06j_*.)
+template <int NW, int PARTS>
+__device__ __forceinline__ double sia_exchange_sums(XChunk* xbase, unsigned xseq, int buf, int changed, int lane, bool publish, int part,
+                                                    int& xfail) {
+  const int xp = lane >> 4, xk = lane & 15;
+  double own = 0.0;
+  if (xk < 8) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) own += (double)g_s.part[buf][w][xk];
+  } else if (xk == 8) {
+    own = (double)changed;
+  }
+  XChunk* const slot = xbase + (size_t)(xseq & 1) * (SIA_X_MAX_PARTS * SIA_X_SLOTS);
+  if (publish && xp == part && xk < 9) sia_xstore(slot + part * SIA_X_SLOTS + xk, own, xseq);
+  double val = own;
+  if (xp != part && xp < PARTS && xk < 9) val = sia_xpoll(slot + xp * SIA_X_SLOTS + xk, xseq, xfail);
+  if (xfail) g_s.xfail = 1;
+  // the parts in a fixed order: every part forms the same sums
+  double xtot = __shfl(val, xk, 64);
+#pragma unroll
+  for (int p = 1; p < PARTS; ++p) xtot += __shfl(val, 16 * p + xk, 64);
+  return xtot;
+}
+#endif
 
 // (A fetch-ahead of the next level's windows -- global_load_lds touches of their corner tiles during iteration 0 -- measured
 // worse, 1.30 against 1.21 ms: the extra gathers cost more L1 look-ups and in-order vmcnt waiting than warm lines give back.)
@@ -233,27 +263,16 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
   // Interpolated reference image around this lane's patch, staged in LDS: the
   // bilinear sample at window pixel (r,c) of the 6x6 neighbourhood (corners unused
   // -> 32 floats = 8 float4 per lane, laid out [8][BLOCK] so a wave reads 1 KiB
-  // contiguous per ds_read_b128).  ref_patch_cache_(y,x) = Bt[y+1][x+1]; the gradients
-  // dx,dy (:133-136) are central differences of Bt, rebuilt in flight.
-  //   q0 = r0 c1..4 | q1 = r1 c0..3 | q2 = r1 c4,5 r2 c0,1 | q3 = r2 c2..5
-  //   q4 = r3 c0..3 | q5 = r3 c4,5 r4 c0,1 | q6 = r4 c2..5 | q7 = r5 c1..4
+  // contiguous per ds_read_b128; which sample goes where: sia_tile_store / sia_tile_store_packed, sia_common.h).
+  // ref_patch_cache_(y,x) = Bt[y+1][x+1]; the gradients dx,dy (:133-136) are central differences of Bt, rebuilt in flight.
   __shared__ float4 s_bt[8][BLOCK];
 
   int n = a.n[b];
   n = n > a.n_stride ? a.n_stride : n;  // contract: n <= n_stride (svo_hip.h); never read the next problem's rows
   const svo_hip_sia_params P = a.P;
 
-  if (n <= 0) {  // sparse_img_align.cpp:47-51: nothing to track, pose untouched
-    if (tid == 0 && part == 0) {
-      for (int k = 0; k < 12; ++k) a.T_out[12 * b + k] = a.T_in[12 * b + k];
-      if (a.H_out)
-        for (int k = 0; k < 36; ++k) a.H_out[36 * b + k] = 0.0;
-      a.n_tracked[b] = 0;
-      if (a.iters)
-        for (int k = 0; k < SVO_HIP_MAX_LEVELS; ++k) a.iters[SVO_HIP_MAX_LEVELS * b + k] = 0;
-      if (a.chi2) a.chi2[b] = 1e10;
-      if (a.status) a.status[b] = 0;
-    }
+  if (n <= 0) {
+    if (tid == 0 && part == 0) sia_untracked(a, b);
     return;
   }
 
@@ -277,7 +296,7 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
   }
   // normalised coordinates of xyz_ref: all of Frame::jacobian_xyz2uv (frame.h:116-138)
   // is a function of (x/z, y/z, 1/z)
-  const double rz = sia_rcp(Z);
+  const double rz = fast_rcp(Z);
   const sia_acc zi = (sia_acc)rz;
   const sia_acc xn = (sia_acc)(X * rz);
   const sia_acc yn = (sia_acc)(Y * rz);
@@ -287,10 +306,10 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
   if (tid == 0) {
 #pragma unroll
     for (int k = 0; k < SVO_HIP_MAX_LEVELS; ++k) {
-      g_s.lw[k] = a.L.w[k];
-      g_s.lh[k] = a.L.h[k];
-      g_s.lp[k] = a.L.pitch[k];
-      g_s.lo[k] = a.L.offset[k];
+      g_s.lv.lw[k] = a.L.w[k];
+      g_s.lv.lh[k] = a.L.h[k];
+      g_s.lv.lp[k] = a.L.pitch[k];
+      g_s.lv.lo[k] = a.L.offset[k];
     }
     for (int k = 0; k < 21; ++k) g_s.H[k] = 0.0;
     g_s.xfail = 0;
@@ -301,6 +320,8 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
   double R[9], tr[3];
   {
     double q[4];
+    // (sia_model_init of sia_common.h written out: the call adds an instruction ahead of the level loop and moves every
+    // address after it; without it the headline instantiation has the parent's length and layout, profiles/r10a_*)
     for (int k = 0; k < 9; ++k) R[k] = a.T_in[12 * b + k];
     for (int k = 0; k < 3; ++k) tr[k] = a.T_in[12 * b + 9 + k];
     quat_from_R(R, q);
@@ -331,9 +352,9 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
 #endif
   for (int level = P.max_level; level >= P.min_level; --level) {
     [[maybe_unused]] const long long tl0 = SIA_T();
-    const int cols = g_s.lw[level], rows = g_s.lh[level], pitch = g_s.lp[level];
-    const uint8_t* ref_img = ref_base + g_s.lo[level];
-    const uint8_t* cur_img = cur_base + g_s.lo[level];
+    const int cols = g_s.lv.lw[level], rows = g_s.lv.lh[level], pitch = g_s.lv.lp[level];
+    const uint8_t* ref_img = ref_base + g_s.lv.lo[level];
+    const uint8_t* cur_img = cur_base + g_s.lv.lo[level];
     const float scale = pow2_inv_f32(level);  // == 1.0f / (float)(1 << level), from exponent bits (no division sequence)
     // focal_length / 2^level (:139-140), folded into the per-patch sums
     const sia_acc fl = (sia_acc)(fabs(P.fx) * pow2_inv_f64(level));  // == / 2^level, bit for bit
@@ -372,13 +393,9 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
         } else
 #endif
         {
-          // The reference forms these products in double and rounds to float (:118-121).  u >= 3 here, so su
-          // and sv are multiples of 2^-22: 1-su and 1-sv are exact in f32, and the f32 product of two f32
-          // values is the correctly rounded exact product, like the rounded double product -- bit-identical.
-          const float wtl = (1.f - su) * (1.f - sv);
-          const float wtr = su * (1.f - sv);
-          const float wbl = (1.f - su) * sv;
-          const float wbr = su * sv;
+          // (sampled with sia_bilerp's pinned order, the sums in sia_pix: why this block is not the wave kernel's)
+          float wtl, wtr, wbl, wbr;
+          sia_weights(su, sv, wtl, wtr, wbl, wbr);
           float Bt[6][6];
           float Wp[7], Wc[7];
           cut_row7(rw[0], rbo, Wp);
@@ -404,23 +421,9 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
               Syy += (sia_pix)dy * (sia_pix)dy;
             }
 #if SIA_PACKED
-          s_bt[0][tid] = make_float4(Bt[0][1], Bt[0][3], Bt[0][2], Bt[0][4]);
-          s_bt[1][tid] = make_float4(Bt[1][0], Bt[1][2], Bt[1][1], Bt[1][3]);
-          s_bt[2][tid] = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][2]);
-          s_bt[3][tid] = make_float4(Bt[2][1], Bt[2][3], Bt[2][4], Bt[2][5]);
-          s_bt[4][tid] = make_float4(Bt[3][0], Bt[3][2], Bt[3][1], Bt[3][3]);
-          s_bt[5][tid] = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][2]);
-          s_bt[6][tid] = make_float4(Bt[4][1], Bt[4][3], Bt[4][4], Bt[4][5]);
-          s_bt[7][tid] = make_float4(Bt[5][1], Bt[5][3], Bt[5][2], Bt[5][4]);
+          sia_tile_store_packed(Bt, [&](int k) -> float4& { return s_bt[k][tid]; });
 #else
-          s_bt[0][tid] = make_float4(Bt[0][1], Bt[0][2], Bt[0][3], Bt[0][4]);
-          s_bt[1][tid] = make_float4(Bt[1][0], Bt[1][1], Bt[1][2], Bt[1][3]);
-          s_bt[2][tid] = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][1]);
-          s_bt[3][tid] = make_float4(Bt[2][2], Bt[2][3], Bt[2][4], Bt[2][5]);
-          s_bt[4][tid] = make_float4(Bt[3][0], Bt[3][1], Bt[3][2], Bt[3][3]);
-          s_bt[5][tid] = make_float4(Bt[3][4], Bt[3][5], Bt[4][0], Bt[4][1]);
-          s_bt[6][tid] = make_float4(Bt[4][2], Bt[4][3], Bt[4][4], Bt[4][5]);
-          s_bt[7][tid] = make_float4(Bt[5][1], Bt[5][2], Bt[5][3], Bt[5][4]);
+          sia_tile_store(Bt, [&](int k) -> float4& { return s_bt[k][tid]; });
 #endif
         }
       } else {
@@ -444,6 +447,8 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
       sia_pix gx = 0, gy = 0;
       float c2 = 0.f;
       if (vis) {
+        // (sia_project of sia_common.h written out: called here it moves the register allocation of the distorted
+        // instantiations, <256, false, true, 1> 163 -> 161 VGPRs, the f64 <1024, false, true, 1> 148 -> 156 B of scratch)
         const double xc = R[0] * X + R[1] * Y + R[2] * Z + tr[0];
         const double yc = R[3] * X + R[4] * Y + R[5] * Z + tr[1];
         const double zc = R[6] * X + R[7] * Y + R[8] * Z + tr[2];
@@ -472,15 +477,11 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
         const float u_cur = (float)pu * scale;
         const float v_cur = (float)pv * scale;
         const float fu = floorf(u_cur), fv = floorf(v_cur);
-        // NaN / huge coordinates fail the comparisons below like the int tests do
-        if (fu - 3.f >= 0.f && fv - 3.f >= 0.f && fu + 3.f < (float)cols && fv + 3.f < (float)rows) {
+        if (sia_inside3(fu, fv, cols, rows)) {
           m = true;
           const int u_i = (int)fu, v_i = (int)fv;
-          const float su = u_cur - fu, sv = v_cur - fv;
-          const float wtl = (1.f - su) * (1.f - sv);  // == the reference's rounded double products (:200-203), see above
-          const float wtr = su * (1.f - sv);
-          const float wbl = (1.f - su) * sv;
-          const float wbr = su * sv;
+          float wtl, wtr, wbl, wbr;
+          sia_weights(u_cur - fu, v_cur - fv, wtl, wtr, wbl, wbr);
           {
 #if SIA_PACKED
           // Two pixels per instruction (v_pk_mul/fma/add_f32): columns x = 0, 2 in one register pair, x = 1, 3 in
@@ -495,6 +496,8 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
           uint64_t k0 = 0, k1 = 0, kup = 0;
           int bo = 0;
           if (WC) {
+            // (sia_wc_seek / sia_wc_row / sia_jres_partials of sia_common.h written out in this kernel's iteration: with the
+            // calls the headline came out 0.4 .. 0.5 % slower in three of eight comparisons, profiles/r10a_* section 4)
             int r0 = (v_i - 2) - wc_v0;  // first cached row needed
             bo = (u_i - 2) - wc_u0;      // first cached byte needed
             if (!(r0 >= 0 && r0 <= 2 && bo >= 0 && bo <= 7)) {
@@ -616,19 +619,7 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
             for (int r = 0; r < 5; ++r) cut_row5_plain(cw[r], cbo, W[r]);
           }
           float Bt[6][6];
-          {
-            const float4 q0 = s_bt[0][tid], q1 = s_bt[1][tid], q2 = s_bt[2][tid], q3 = s_bt[3][tid];
-            const float4 q4 = s_bt[4][tid], q5 = s_bt[5][tid], q6 = s_bt[6][tid], q7 = s_bt[7][tid];
-            Bt[0][0] = Bt[0][5] = Bt[5][0] = Bt[5][5] = 0.f;
-            Bt[0][1] = q0.x; Bt[0][2] = q0.y; Bt[0][3] = q0.z; Bt[0][4] = q0.w;
-            Bt[1][0] = q1.x; Bt[1][1] = q1.y; Bt[1][2] = q1.z; Bt[1][3] = q1.w;
-            Bt[1][4] = q2.x; Bt[1][5] = q2.y; Bt[2][0] = q2.z; Bt[2][1] = q2.w;
-            Bt[2][2] = q3.x; Bt[2][3] = q3.y; Bt[2][4] = q3.z; Bt[2][5] = q3.w;
-            Bt[3][0] = q4.x; Bt[3][1] = q4.y; Bt[3][2] = q4.z; Bt[3][3] = q4.w;
-            Bt[3][4] = q5.x; Bt[3][5] = q5.y; Bt[4][0] = q5.z; Bt[4][1] = q5.w;
-            Bt[4][2] = q6.x; Bt[4][3] = q6.y; Bt[4][4] = q6.z; Bt[4][5] = q6.w;
-            Bt[5][1] = q7.x; Bt[5][2] = q7.y; Bt[5][3] = q7.z; Bt[5][4] = q7.w;
-          }
+          sia_tile_load([&](int k) { return s_bt[k][tid]; }, Bt);
 #pragma unroll
           for (int y = 0; y < 4; ++y)
 #pragma unroll
@@ -644,7 +635,7 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
         }
       }
       // -- workgroup reduction of Jres, chi2, n_meas ------------------------
-      // Jres -= J res with J = dx*a + dy*b, a = fl*jac.row(0), b = fl*jac.row(1)
+      // Jres -= J res with J = dx*a + dy*b, a = fl*jac.row(0), b = fl*jac.row(1) (sia_jres_partials written out, see above)
       {
         // dx, dy carry a factor 0.5 (central difference)
         const sia_acc gsc = (sia_acc)0.5 * fl * gmask;
@@ -679,27 +670,8 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
       [[maybe_unused]] double xtot = 0.0;  // PARTS > 1: lane k < 9 of every wave holds the FRAME's sum k (k = 8: "changed" anywhere)
 #ifndef SVO_HOST_MATH_TEST
       if constexpr (PARTS > 1) {
-        // every wave takes part (no second barrier): lane = (part xp, sum xk); the workgroup's own sums come from LDS, wave
-        // `sw` publishes them, the other parts' are polled.  (One polling wave per workgroup that hands the sums to the others
-        // through LDS behind a second barrier measured the same: 0.0938 against 0.0949 ms, profiles/r06j_*.)
         ++xseq;
-        const int xp = lane >> 4, xk = lane & 15;
-        double own = 0.0;
-        if (xk < 8) {
-#pragma unroll
-          for (int w = 0; w < NW; ++w) own += (double)g_s.part[buf][w][xk];
-        } else if (xk == 8) {
-          own = (double)changed;
-        }
-        XChunk* const slot = xbase + (size_t)(xseq & 1) * (SIA_X_MAX_PARTS * SIA_X_SLOTS);
-        if (wave == sw && xp == part && xk < 9) sia_xstore(slot + part * SIA_X_SLOTS + xk, own, xseq);
-        double val = own;
-        if (xp != part && xp < PARTS && xk < 9) val = sia_xpoll(slot + xp * SIA_X_SLOTS + xk, xseq, xfail);
-        if (xfail) g_s.xfail = 1;
-        // the parts in a fixed order: every part forms the same sums
-        xtot = __shfl(val, xk, 64);
-#pragma unroll
-        for (int p = 1; p < PARTS; ++p) xtot += __shfl(val, 16 * p + xk, 64);
+        xtot = sia_exchange_sums<NW, PARTS>(xbase, xseq, buf, changed, lane, wave == sw, part, xfail);
         changed = readlane_f64<8>(xtot) != 0.0;
       }
 #endif
@@ -712,19 +684,7 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
         // out of it and stay live across it -- 35 VGPRs, the difference between 3 and 4 waves per SIMD)
         sia_acc zi_ = zi, xn_ = xn, yn_ = yn;
         asm volatile("" : "+v"(zi_), "+v"(xn_), "+v"(yn_));
-        const sia_acc one = 1, zero = 0;
-        const sia_acc ja[6] = {-zi_ * fl, zero, xn_ * zi_ * fl, xn_ * yn_ * fl, -(one + xn_ * xn_) * fl, yn_ * fl};
-        const sia_acc jb[6] = {zero, -zi_ * fl, yn_ * zi_ * fl, (one + yn_ * yn_) * fl, -xn_ * yn_ * fl, -xn_ * fl};
-        // a patch outside the current image: S = 0, exact zeros in every entry
-        const sia_acc sxx = m ? (sia_acc)Sxx : zero, sxy = m ? (sia_acc)Sxy : zero, syy = m ? (sia_acc)Syy : zero;
-        sia_acc hp[24];
-        sia_patch_hessian<sia_acc>(ja, jb, sxx, sxy, syy, hp);
-        hp[21] = hp[22] = hp[23] = zero;
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-          const sia_acc tot = wave_reduce8(hp + 8 * g, lane);
-          if ((lane & 7) == 0) g_s.Hpart[wave][8 * g + (lane >> 3)] = tot;
-        }
+        sia_hessian_partials(zi_, xn_, yn_, fl, m, Sxx, Sxy, Syy, lane, wave);
         inH = (int)m;
         __syncthreads();
         if constexpr (PARTS > 1) {
@@ -756,6 +716,7 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
       // the old translation).  Each forms the totals, x = H^-1 Jres and the stop / rollback decision for itself (the
       // same ~40 instructions on the same LDS words, hence the same decision) and then runs its half: the dependent
       // chain between the two barriers is ~130 instructions instead of ~310, on two SIMDs.
+      // (stays inline: the two-wave step reads and writes the whole solver state of the loop -- R, tr, m_cur, m_old, chi2_prev, stop, done)
       const int swb = (NW > 1) ? (sw + 1) % NW : sw;
       const bool rot_wave = wave == sw, trans_wave = wave == swb;
       int m_next = m_cur;  // (both solver waves compute it; the others read it from LDS behind the barrier)
@@ -773,17 +734,14 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
         const double b3 = readlane_f64<3>(colsum), b4 = readlane_f64<4>(colsum), b5 = readlane_f64<5>(colsum);
         const float chi2_sum = (float)readlane_f64<6>(colsum);
         const int n_meas = (int)readlane_f64<7>(colsum);
-        double xi;
-        {
-          const double* row = &g_s.Hinv[6 * (lane < 6 ? lane : 0)];
-          xi = row[0] * b0 + row[1] * b1 + row[2] * b2 + row[3] * b3 + row[4] * b4 + row[5] * b5;
-        }
+        const double xi = sia_solve_rows(g_s.Hinv, b0, b1, b2, b3, b4, b5, lane);
         const double x0 = readlane_f64<0>(xi), x1 = readlane_f64<1>(xi), x2 = readlane_f64<2>(xi);
         const double x3 = readlane_f64<3>(xi), x4 = readlane_f64<4>(xi), x5 = readlane_f64<5>(xi);
         n_meas_last = n_meas;
         const double new_chi2 = (double)(chi2_sum / (float)n_meas);
         if (isnan(x0)) stop = 1;  // solve(), :248-249
         const SplitModel& sm = g_s.sm;
+        // (the rule is the wave kernel's, what follows it is not: here a rollback swaps parity buffers between two solver waves)
         const bool rollback = (iter > 0 && new_chi2 > chi2_prev) || stop;
         if (rollback) {
           m_next = m_old;  // model = old_model: the buffer the last update came from
@@ -792,7 +750,7 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
           m_next = m_cur ^ 1;
           m_old = m_cur;
           chi2_prev = new_chi2;
-          const double nm = fmax(fmax(fmax(fabs(x0), fabs(x1)), fmax(fabs(x2), fabs(x3))), fmax(fabs(x4), fabs(x5)));
+          const double nm = sia_norm_max6(x0, x1, x2, x3, x4, x5);
           if (nm <= P.eps) done = 1;
         }
         // update(): T_new = T_old * SE3::exp(-x_)  (:253-258), each wave its half
@@ -888,11 +846,7 @@ __global__ void __launch_bounds__(BLOCK, PARTS > 1 ? 1 : ((DIST && BLOCK < 1024)
   }
 
   if (tid == 0 && part == 0) {
-    for (int k = 0; k < 9; ++k) a.T_out[12 * b + k] = R[k];
-    for (int k = 0; k < 3; ++k) a.T_out[12 * b + 9 + k] = tr[k];
-    if (a.H_out)
-      for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) a.H_out[36 * b + i * 6 + j] = g_s.H[sym6_rt(i, j)];
+    sia_write_pose_and_H(a, b, R, tr);
 #ifdef SIA_PROFILE
     prof[6] = SIA_T() - t_begin;
     if (a.H_out)

@@ -2,8 +2,10 @@
 // with at most 192 patches (64 under a distorted camera model); everything else -- single frames, the 200-patch
 // headline workload -- runs the workgroup-per-problem kernel of sparse_align.hip (sia_wave_applies() below).
 //
-// Same algorithm and numerics as sparse_align.hip (svo::SparseImgAlign::run + the Gauss-Newton loop of
-// vk::NLLSSolver, svo/src/sparse_img_align.cpp:43-258); what changes is who does the work.  There a
+// Same algorithm as sparse_align.hip (svo::SparseImgAlign::run + the Gauss-Newton loop of vk::NLLSSolver,
+// svo/src/sparse_img_align.cpp:43-258), the per-patch pieces from the same definitions (sia_common.h); one known difference
+// in the numerics: the bilinear sample here is fused by the compiler in its own order, not in sia_bilerp's pinned one
+// (DESIGN.md, K1).  What changes is who does the work.  There a
 // workgroup of four waves owns a frame, one lane per patch, and every iteration pays two workgroup
 // barriers and a serial solve that three of the four waves sit out.  Here a frame is ONE wave:
 //
@@ -50,13 +52,8 @@ struct WaveLds {
   float red[24];         // wave totals of the 21 H entries, handed from the lanes that hold them to lanes 0..20
   double Hinv[36];       // H^-1, row-major
   double A[36];          // Gauss-Jordan scratch
-  long long lo[SVO_HIP_MAX_LEVELS];
-  int lw[SVO_HIP_MAX_LEVELS], lh[SVO_HIP_MAX_LEVELS], lp[SVO_HIP_MAX_LEVELS];
+  SiaLevels lv;
 };
-
-__device__ __forceinline__ float readlane_f32(float v, int src) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
 
 template <int PPL, bool DIST>
 __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a, const int n_slots) {
@@ -66,9 +63,7 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
 
   // Interpolated reference image around every patch: the bilinear sample at window pixel (r,c) of the 6x6
   // neighbourhood, corners unused -> 32 floats = 8 float4 per patch, laid out [8][n_slots] so a wave reads
-  // 1 KiB contiguous per ds_read_b128 (same packing as sparse_align.hip):
-  //   q0 = r0 c1..4 | q1 = r1 c0..3 | q2 = r1 c4,5 r2 c0,1 | q3 = r2 c2..5
-  //   q4 = r3 c0..3 | q5 = r3 c4,5 r4 c0,1 | q6 = r4 c2..5 | q7 = r5 c1..4
+  // 1 KiB contiguous per ds_read_b128 (the plain order of sia_tile_store, sia_common.h).
   // Patches 64k..64k+63 (the lanes' k-th patches) form one block [8][64] float4, so that every address is
   // the lane's base plus a compile-time offset; the last block is [8][last_n], last_n = n_slots - 64 (PPL-1).
   SVO_DYNAMIC_LDS(float4, s_bt);
@@ -80,17 +75,8 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
   n = n > a.n_stride ? a.n_stride : n;  // contract: n <= n_stride (svo_hip.h)
   const svo_hip_sia_params P = a.P;
 
-  if (n <= 0) {  // sparse_img_align.cpp:47-51: nothing to track, pose untouched
-    if (lane == 0) {
-      for (int k = 0; k < 12; ++k) a.T_out[12 * b + k] = a.T_in[12 * b + k];
-      if (a.H_out)
-        for (int k = 0; k < 36; ++k) a.H_out[36 * b + k] = 0.0;
-      a.n_tracked[b] = 0;
-      if (a.iters)
-        for (int k = 0; k < SVO_HIP_MAX_LEVELS; ++k) a.iters[SVO_HIP_MAX_LEVELS * b + k] = 0;
-      if (a.chi2) a.chi2[b] = 1e10;
-      if (a.status) a.status[b] = 0;
-    }
+  if (n <= 0) {
+    if (lane == 0) sia_untracked(a, b);
     return;
   }
 
@@ -107,7 +93,7 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
       p.Y = a.xyz[3 * fo + 1];
       p.Z = a.xyz[3 * fo + 2];
     }
-    const double rz = sia_rcp(p.Z);  // (as sparse_align.hip: the two kernels keep the same per-patch arithmetic)
+    const double rz = fast_rcp(p.Z);
     p.zi = (float)rz;
     p.xn = (float)(p.X * rz);
     p.yn = (float)(p.Y * rz);
@@ -126,10 +112,10 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < SVO_HIP_MAX_LEVELS; ++k) {
-      g.lw[k] = a.L.w[k];
-      g.lh[k] = a.L.h[k];
-      g.lp[k] = a.L.pitch[k];
-      g.lo[k] = a.L.offset[k];
+      g.lv.lw[k] = a.L.w[k];
+      g.lv.lh[k] = a.L.h[k];
+      g.lv.lp[k] = a.L.pitch[k];
+      g.lv.lo[k] = a.L.offset[k];
     }
     if (a.iters)
       for (int k = 0; k < SVO_HIP_MAX_LEVELS; ++k) a.iters[SVO_HIP_MAX_LEVELS * b + k] = 0;
@@ -139,12 +125,10 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
   // lives in SGPRs (wave-uniform, v_readfirstlane)
   double R[9], tr[3];
   {
-    double q[4], Rm[9];
-    for (int k = 0; k < 9; ++k) Rm[k] = a.T_in[12 * b + k];
-    for (int k = 0; k < 3; ++k) tr[k] = sia_uni(a.T_in[12 * b + 9 + k]);
-    quat_from_R(Rm, q);
-    quat_to_R(q, Rm);
-    for (int k = 0; k < 9; ++k) R[k] = sia_uni(Rm[k]);
+    double q[4], Rm[9], tm[3];
+    sia_model_init(a.T_in + 12 * b, q, Rm, tm);
+    for (int k = 0; k < 3; ++k) tr[k] = uniform_f64(tm[k]);
+    for (int k = 0; k < 9; ++k) R[k] = uniform_f64(Rm[k]);
     if (lane == 0) {
       for (int k = 0; k < 4; ++k) g.q[k] = g.oq[k] = q[k];
       for (int k = 0; k < 3; ++k) g.t[k] = g.ot[k] = tr[k];
@@ -157,9 +141,9 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
   __syncthreads();  // a single wave: orders the LDS writes above before the reads below
 
   for (int level = P.max_level; level >= P.min_level; --level) {
-    const int cols = g.lw[level], rows = g.lh[level], pitch = g.lp[level];
-    const uint8_t* ref_img = ref_base + g.lo[level];
-    const uint8_t* cur_img = cur_base + g.lo[level];
+    const int cols = g.lv.lw[level], rows = g.lv.lh[level], pitch = g.lv.lp[level];
+    const uint8_t* ref_img = ref_base + g.lv.lo[level];
+    const uint8_t* cur_img = cur_base + g.lv.lo[level];
     const float scale = pow2_inv_f32(level);  // == 1.0f / (float)(1 << level), from exponent bits (no division sequence)
     // focal_length / 2^level (:139-140), folded into the per-patch sums
     const float fl = (float)(fabs(P.fx) * pow2_inv_f64(level));  // == / 2^level, bit for bit
@@ -203,31 +187,10 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
       Patch& p = pt[k];
       p.wc_v0 = -100000;  // the cache holds rows of the previous level
       const bool will_see = p.vis || inb_k[k];
-      const double xc = R[0] * p.X + R[1] * p.Y + R[2] * p.Z + tr[0];
-      const double yc = R[3] * p.X + R[4] * p.Y + R[5] * p.Z + tr[1];
-      const double zc = R[6] * p.X + R[7] * p.Y + R[8] * p.Z + tr[2];
-      double izc = __builtin_amdgcn_rcp(zc);
-      izc = fma(fma(-zc, izc, 1.0), izc, izc);
-      izc = fma(fma(-zc, izc, 1.0), izc, izc);
       double pu, pv;
-      if (DIST) {
-        Cam cm;
-        cm.fx = P.fx; cm.fy = P.fy; cm.cx = P.cx; cm.cy = P.cy;
-        cm.width = 0; cm.height = 0;
-        cm.model = P.cam_model;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) cm.d[j] = P.d[j];
-        const double uvn[2] = {xc * izc, yc * izc};
-        double pxd[2];
-        world2cam_uv(cm, uvn, pxd);
-        pu = pxd[0];
-        pv = pxd[1];
-      } else {
-        pu = P.fx * (xc * izc) + P.cx;
-        pv = P.fy * (yc * izc) + P.cy;
-      }
+      sia_project<DIST>(P, R, tr, p.X, p.Y, p.Z, pu, pv);
       const float fu = floorf((float)pu * scale), fv = floorf((float)pv * scale);
-      const bool okc = will_see && fu - 3.f >= 0.f && fv - 3.f >= 0.f && fu + 3.f < (float)cols && fv + 3.f < (float)rows;
+      const bool okc = will_see && sia_inside3(fu, fv, cols, rows);
       const int cu = okc ? (int)fu : 3, cv = okc ? (int)fv : 3;
       const int v0 = cv - 3, u0 = run_start(cu - 3, 7);
       load_window12<7>(cur_img, pitch, u0, v0, p.wc);
@@ -244,12 +207,10 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
         p.vis = true;
         p.gmask = 1.f;
         const float su = su_k[k], sv = sv_k[k];
-        // == the reference's rounded double products (:118-121): u >= 3, so su, sv are multiples of 2^-22,
-        // 1-su and 1-sv are exact in f32 and an f32 product is the correctly rounded exact product
-        const float wtl = (1.f - su) * (1.f - sv);
-        const float wtr = su * (1.f - sv);
-        const float wbl = (1.f - su) * sv;
-        const float wbr = su * sv;
+        float wtl, wtr, wbl, wbr;
+        sia_weights(su, sv, wtl, wtr, wbl, wbr);
+        // (the sample left to the compiler's own fusing, not sia_bilerp's pinned order: why this block is not the scalar
+        // template block of sia_kernel)
         float Bt[6][6];
         float Wp[7], Wc[7];
         cut_row7(rw[k][0], (uint32_t)sel_ref[k], Wp);
@@ -276,6 +237,8 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
             Syy += dy * dy;
           }
         p.Sxx = Sxx; p.Sxy = Sxy; p.Syy = Syy;
+        // (sia_tile_store / sia_tile_load written out, here and in the evaluation: through the helpers <2, false> goes
+        // 194 -> 192 VGPRs)
         SIA_BT(k, 0) = make_float4(Bt[0][1], Bt[0][2], Bt[0][3], Bt[0][4]);
         SIA_BT(k, 1) = make_float4(Bt[1][0], Bt[1][1], Bt[1][2], Bt[1][3]);
         SIA_BT(k, 2) = make_float4(Bt[1][4], Bt[1][5], Bt[2][0], Bt[2][1]);
@@ -311,61 +274,23 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
         bool m = false;
         float gx = 0.f, gy = 0.f, c2 = 0.f;
         if (p.vis) {
-          const double xc = R[0] * p.X + R[1] * p.Y + R[2] * p.Z + tr[0];
-          const double yc = R[3] * p.X + R[4] * p.Y + R[5] * p.Z + tr[1];
-          const double zc = R[6] * p.X + R[7] * p.Y + R[8] * p.Z + tr[2];
-          // cam_->world2cam(project2d(xyz)) (:183), one reciprocal: v_rcp_f64 + two Newton steps
-          double izc = __builtin_amdgcn_rcp(zc);
-          izc = fma(fma(-zc, izc, 1.0), izc, izc);
-          izc = fma(fma(-zc, izc, 1.0), izc, izc);
           double pu, pv;
-          if (DIST) {
-            Cam cm;
-            cm.fx = P.fx; cm.fy = P.fy; cm.cx = P.cx; cm.cy = P.cy;
-            cm.width = 0; cm.height = 0;
-            cm.model = P.cam_model;
-#pragma unroll
-            for (int j = 0; j < 5; ++j) cm.d[j] = P.d[j];
-            const double uvn[2] = {xc * izc, yc * izc};
-            double pxd[2];
-            world2cam_uv(cm, uvn, pxd);
-            pu = pxd[0];
-            pv = pxd[1];
-          } else {
-            pu = P.fx * (xc * izc) + P.cx;
-            pv = P.fy * (yc * izc) + P.cy;
-          }
+          sia_project<DIST>(P, R, tr, p.X, p.Y, p.Z, pu, pv);
           const float u_cur = (float)pu * scale;
           const float v_cur = (float)pv * scale;
           const float fu = floorf(u_cur), fv = floorf(v_cur);
-          // NaN / huge coordinates fail the comparisons below like the int tests do
-          if (fu - 3.f >= 0.f && fv - 3.f >= 0.f && fu + 3.f < (float)cols && fv + 3.f < (float)rows) {
+          if (sia_inside3(fu, fv, cols, rows)) {
             m = true;
             const int u_i = (int)fu, v_i = (int)fv;
-            const float su = u_cur - fu, sv = v_cur - fv;
-            const float wtl = (1.f - su) * (1.f - sv);  // == the reference's rounded double products (:200-203)
-            const float wtr = su * (1.f - sv);
-            const float wbl = (1.f - su) * sv;
-            const float wbr = su * sv;
+            float wtl, wtr, wbl, wbr;
+            sia_weights(u_cur - fu, v_cur - fv, wtl, wtr, wbl, wbr);
             float W[5][5];
-            int r0 = (v_i - 2) - p.wc_v0;  // first cached row needed
-            int bo = (u_i - 2) - p.wc_u0;  // first cached byte needed
-            if (!(r0 >= 0 && r0 <= 2 && bo >= 0 && bo <= 7)) {
-              p.wc_v0 = v_i - 3;
-              p.wc_u0 = run_start(u_i - 3, 7);
-              load_window12<7>(cur_img, pitch, p.wc_u0, p.wc_v0, p.wc);
-              r0 = 1;
-              bo = (u_i - 2) - p.wc_u0;
-            }
+            int r0, bo;
+            sia_wc_seek(p.wc, p.wc_u0, p.wc_v0, cur_img, pitch, u_i, v_i, r0, bo);
             const uint64_t k0 = SVO_BALLOT_ACTIVE(r0 == 0), k1 = SVO_BALLOT_ACTIVE(r0 == 1);
             const uint64_t kup = SVO_BALLOT_ACTIVE(bo >= 4);
 #pragma unroll
-            for (int r = 0; r < 5; ++r) {
-              const uint32_t d0 = sel_e64(k0, p.wc[r][0], sel_e64(k1, p.wc[r + 1][0], p.wc[r + 2][0]));
-              const uint32_t d1 = sel_e64(k0, p.wc[r][1], sel_e64(k1, p.wc[r + 1][1], p.wc[r + 2][1]));
-              const uint32_t d2 = sel_e64(k0, p.wc[r][2], sel_e64(k1, p.wc[r + 1][2], p.wc[r + 2][2]));
-              cut_row5(d0, d1, d2, bo, kup, W[r]);
-            }
+            for (int r = 0; r < 5; ++r) sia_wc_row(p.wc, r, k0, k1, kup, bo, W[r]);
             float Bt[6][6];
             {
               const float4 q0 = SIA_BT(k, 0), q1 = SIA_BT(k, 1), q2 = SIA_BT(k, 2);
@@ -393,22 +318,14 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
               }
           }
         }
-        // Jres -= J res with J = dx*a + dy*b, a = fl*jac.row(0), b = fl*jac.row(1); dx, dy carry a
-        // factor 0.5 (central difference)
         // (the empty asm keeps the compiler from hoisting xn*yn, 1+xn^2, ... of every patch out of the
         // iteration loop: a dozen more registers live across it for a handful of multiplies)
         float zi = p.zi, xn = p.xn, yn = p.yn;
         asm volatile("" : "+v"(zi), "+v"(xn), "+v"(yn));
-        const float gsc = 0.5f * fl * p.gmask;
-        const float gxf = m ? gx * gsc : 0.f, gyf = m ? gy * gsc : 0.f;
-        part[0] += zi * gxf;
-        part[1] += zi * gyf;
-        part[2] += -zi * (xn * gxf + yn * gyf);
-        part[3] += -(xn * yn * gxf + (1.f + yn * yn) * gyf);
-        part[4] += (1.f + xn * xn) * gxf + xn * yn * gyf;
-        part[5] += xn * gyf - yn * gxf;
-        part[6] += c2;
-        part[7] += m ? 16.f : 0.f;
+        float pk[8];
+        sia_jres_partials<float>(zi, xn, yn, fl, p.gmask, m, gx, gy, c2, pk);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) part[j] += pk[j];
         mbits |= (m ? 1u : 0u) << k;
         changed |= ((int)m != p.inH);
       }
@@ -427,8 +344,8 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
           const bool m = (mbits >> k) & 1u;
           float zi = p.zi, xn = p.xn, yn = p.yn;
           asm volatile("" : "+v"(zi), "+v"(xn), "+v"(yn));  // or the ~60 products below are hoisted out of the loop, per patch
-          const float ja[6] = {-zi * fl, 0.f, xn * zi * fl, xn * yn * fl, -(1.f + xn * xn) * fl, yn * fl};
-          const float jb[6] = {0.f, -zi * fl, yn * zi * fl, (1.f + yn * yn) * fl, -xn * yn * fl, -xn * fl};
+          float ja[6], jb[6];
+          sia_jac_rows<float>(zi, xn, yn, fl, ja, jb);
           // (a patch outside the current image: S = 0, exact zeros)
           float hk[21];
           sia_patch_hessian<float>(ja, jb, m ? p.Sxx : 0.f, m ? p.Sxy : 0.f, m ? p.Syy : 0.f, hk);
@@ -442,35 +359,11 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
           if ((lane & 7) == 0) g.red[8 * gq + (lane >> 3)] = t8;
         }
         SVO_WAVE_LDS_FENCE();  // same-wave LDS hand-over: keep the order
-        // H^-1 by Gauss-Jordan on a 6x6 tile held one element per lane (36 lanes), LDS as the row/column
-        // exchange: a few registers instead of the ~90 a register LDL^T keeps live, which matters here
-        // because the lane also carries the state of up to four patches.  A zero pivot contributes nothing,
-        // like the D^-1 step of Eigen's LDLT::solve.  Runs when the set of patches inside the image changes
-        // (about once per level).
+        // H^-1 through LDS (sia_gauss_jordan6), not a register LDL^T: the lane also carries the state of up to four
+        // patches.  Runs when the set of patches inside the image changes (about once per level).
         if (lane < 21) g.H[lane] = (double)g.red[lane];
         SVO_WAVE_LDS_FENCE();
-        const int gi = lane / 6, gj = lane - 6 * gi;
-        if (lane < 36) {
-          g.A[lane] = g.H[sym6_rt(gi, gj)];
-          g.Hinv[lane] = (gi == gj) ? 1.0 : 0.0;
-        }
-        for (int kk = 0; kk < 6; ++kk) {
-          SVO_WAVE_LDS_FENCE();
-          if (lane < 36) {
-            const double pv = g.A[kk * 6 + kk];
-            const double aik = g.A[gi * 6 + kk];
-            const double akj = g.A[kk * 6 + gj];
-            const double bkj = g.Hinv[kk * 6 + gj];
-            const double aij = g.A[lane];
-            const double bij = g.Hinv[lane];
-            const double ip = (fabs(pv) > 2.2250738585072014e-308) ? sia_rcp(pv) : 0.0;
-            const double na = (gi == kk) ? akj * ip : aij - aik * (akj * ip);
-            const double nb = (gi == kk) ? bkj * ip : bij - aik * (bkj * ip);
-            SVO_LANES_LDS_FENCE();
-            g.A[lane] = na;
-            g.Hinv[lane] = nb;
-          }
-        }
+        sia_gauss_jordan6(g.H, g.A, g.Hinv, lane);
         SVO_WAVE_LDS_FENCE();
       }
       ++evals;
@@ -483,12 +376,7 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
         const double b3 = (double)readlane_f32(tot, 24), b4 = (double)readlane_f32(tot, 32), b5 = (double)readlane_f32(tot, 40);
         const float chi2_sum = readlane_f32(tot, 48);
         const int n_meas = (int)readlane_f32(tot, 56);
-        // x_ = H_.ldlt().solve(Jres_) (:247), here x = H^-1 Jres: lane i (<6) owns row i
-        double xi;
-        {
-          const double* row = &g.Hinv[6 * (lane < 6 ? lane : 0)];
-          xi = row[0] * b0 + row[1] * b1 + row[2] * b2 + row[3] * b3 + row[4] * b4 + row[5] * b5;
-        }
+        const double xi = sia_solve_rows(g.Hinv, b0, b1, b2, b3, b4, b5, lane);
         const double x0 = readlane_f64<0>(xi), x1 = readlane_f64<1>(xi), x2 = readlane_f64<2>(xi);
         const double x3 = readlane_f64<3>(xi), x4 = readlane_f64<4>(xi), x5 = readlane_f64<5>(xi);
         n_meas_last = n_meas;
@@ -496,6 +384,7 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
         const double new_chi2 = (double)(chi2_sum / (float)n_meas);
         if (isnan(x0)) stop = 1;  // solve(), :248-249
         double q[4];
+        // (the rule is sia_kernel's, what follows it is not: one wave, old_model is a copy in LDS, not a parity buffer)
         if ((iter > 0 && new_chi2 > chi2_prev) || stop) {
           // rollback: model = old_model
 #pragma unroll
@@ -527,8 +416,7 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
             for (int k = 0; k < 3; ++k) g.ot[k] = ot[k];
           }
           chi2_prev = new_chi2;
-          // vk::norm_max(x_) <= eps_
-          const double nm = fmax(fmax(fmax(fabs(x0), fabs(x1)), fmax(fabs(x2), fabs(x3))), fmax(fabs(x4), fabs(x5)));
+          const double nm = sia_norm_max6(x0, x1, x2, x3, x4, x5);
           if (nm <= P.eps) done = 1;
         }
         double Rm[9];
@@ -540,9 +428,9 @@ __global__ void __launch_bounds__(64, SIAW_MINW) sia_wave_kernel(const SiaArgs a
           for (int k = 0; k < 3; ++k) g.t[k] = tr[k];
         }
 #pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = sia_uni(Rm[k]);
+        for (int k = 0; k < 9; ++k) R[k] = uniform_f64(Rm[k]);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) tr[k] = sia_uni(tr[k]);
+        for (int k = 0; k < 3; ++k) tr[k] = uniform_f64(tr[k]);
       }
       if (done) break;
     }

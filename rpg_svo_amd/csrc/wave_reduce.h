@@ -57,6 +57,14 @@ __device__ __forceinline__ double mk_f64(uint32_t lo, uint32_t hi) {
 __device__ __forceinline__ uint32_t lo32(double v) { return (uint32_t)__double_as_longlong(v); }
 __device__ __forceinline__ uint32_t hi32(double v) { return (uint32_t)((unsigned long long)__double_as_longlong(v) >> 32); }
 
+// A wave-uniform value computed by the VALU lives in a VGPR pair; read back through v_readfirstlane its dwords stay in
+// SGPRs (a pose is 12 to 38 doubles: in VGPRs that many register pairs per lane next to the patches / observations)
+__device__ __forceinline__ double uniform_f64(double v) {
+  const uint32_t l = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo32(v));
+  const uint32_t h = (uint32_t)__builtin_amdgcn_readfirstlane((int)hi32(v));
+  return mk_f64(l, h);
+}
+
 // lanes < 32: a[l] + a[l+32];  lanes >= 32: b[l-32] + b[l]
 __device__ __forceinline__ double swap32_add(double a, double b) {
   auto s0 = __builtin_amdgcn_permlane32_swap(lo32(a), lo32(b), false, false);
