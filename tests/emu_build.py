@@ -24,7 +24,8 @@ UNITS = ("common", "pyramid", "map_mirror", "matcher", "feature_align", "depth_f
 # batches beyond 8192 seeds.
 # ("SIA_F64_PARTIALS",) -- the reference-width build of K1 (csrc/sparse_align.hip: per-pixel products, patch sums and SE3::exp
 # in f64, the scalar pixel loop instead of the packed one), the library behind the benchmark's `roofline_f64_build` figure.
-# Only sparse_align.hip reads the define: the K1 tests (test_sparse_align_emulated.py, test_emulated_shapes.py) run builds 0 and 2.
+# Only sparse_align.hip reads the define: the K1 tests (tests/k1_emulated.py's K1_BUILDS: test_sparse_align_emulated.py,
+# test_k1_level_arith_emulated.py, test_emulated_shapes.py) run builds 0 and 2 on the cases tests/k1_cases.py gives them.
 BUILDS = [(), ("ALIGN_WAVE_MAX_M_VALUE=0",), ("SIA_F64_PARTIALS",)]
 BUILD_IDS = ["default", "lane_kernel_with_finish", "reference_width"]
 

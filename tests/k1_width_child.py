@@ -1,9 +1,9 @@
 """TEST INFRASTRUCTURE, not a test.  Usage: SVO_HIP_LIB=<library> python k1_width_child.py OUT.npz
 
-rpg_svo_amd.capi binds its library when it is imported, so another build of it needs a process of its own: this one runs every
-case of tests/k1_width_cases.py through helpers.run_hip on the library SVO_HIP_LIB names (the reference-width build of K1,
-rpg_svo_amd/lib/variants/libsvo_hip_SIA_F64_PARTIALS.so, for tests/test_sparse_align_width_gpu.py) and writes pose, iters,
-n_tracked, status, H and chi2 of each as "<case>/<kernel>/<field>", plus its wall time.  Nothing here catches an error of a
+rpg_svo_amd.capi binds its library when it is imported, so another build of it needs a process of its own: this one runs the
+variant pairs of tests/k1_cases.py's table through tests/k1_device.py on the library SVO_HIP_LIB names (the reference-width build
+of K1, rpg_svo_amd/lib/variants/libsvo_hip_SIA_F64_PARTIALS.so, for tests/test_sparse_align_width_gpu.py) and writes the
+K1Answer of each as "<case>/<schedule>/<auto|workgroup|again>/<field>", plus its wall time.  Nothing here catches an error of a
 launch: the first one ends the process with a non-zero status."""
 import os
 import sys
@@ -16,16 +16,11 @@ for p in (HERE, os.path.dirname(HERE)):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+KERNELS = {"var": ("auto", "auto"), "var_wg": ("workgroup", "workgroup"), "var_twice": ("again", "auto")}   # backend -> (tag, kernel)
 
-def run_case(name, kernel, out, tag=None):
-    import k1_width_cases
-    from helpers import run_hip
-    b, (hi, lo, n_iter) = k1_width_cases.CASES[name]()
-    T, res, _ = run_hip(b, hi, lo, n_iter, kernel=kernel)
-    key = f"{name}/{tag or kernel}/"
-    out[key + "pose"] = T
-    for field in ("iters", "n_tracked", "status", "H", "chi2"):
-        out[key + field] = getattr(res, field).cpu().numpy()
+
+def key(name, schedule, tag):
+    return f"{name}/{'-'.join(map(str, schedule))}/{tag}/"
 
 
 def main(path):
@@ -34,19 +29,20 @@ def main(path):
     want = os.environ["SVO_HIP_LIB"]
     assert capi.lib_path() == want, (capi.lib_path(), want)
     capi.load()
-    import k1_width_cases
-    out = {}
-    for name in k1_width_cases.CASES:
-        run_case(name, "auto", out)
-        if name in k1_width_cases.WORKGROUP_TOO:
-            run_case(name, "workgroup", out)
-        if name == k1_width_cases.TWICE:
-            run_case(name, "auto", out, tag="again")
+    import k1_cases
+    import k1_device
+    out, n = {}, 0
+    for backend, (tag, kernel) in KERNELS.items():
+        for name in k1_cases.cases_of(backend):
+            for schedule in k1_cases.schedules_of(name, backend):
+                answer = k1_device.run(k1_cases.case(name), schedule, kernel)
+                out.update({key(name, schedule, tag) + f: a for f, a in answer._asdict().items()})
+                n += 1
     wall = time.perf_counter() - t0
     out["wall_seconds"] = np.float64(wall)
     out["lib_path"] = np.array(capi.lib_path())
     np.savez(path, **out)
-    print(f"k1_width_child: {len(k1_width_cases.CASES)} cases on {capi.lib_path()} in {wall:.1f} s")
+    print(f"k1_width_child: {n} runs on {capi.lib_path()} in {wall:.1f} s")
 
 
 if __name__ == "__main__":

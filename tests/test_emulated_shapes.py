@@ -6,13 +6,12 @@ AddressSanitizer, too."""
 import numpy as np
 import pytest
 
-import k1_width_cases
-from helpers import run_oracle
+import k1_cases as k1
+import k1_emulated
 from oracle import pytrack
-from rpg_svo_amd import capi, se3, synth
+from rpg_svo_amd import capi, synth
 from test_fast_emulated import detect
 from test_pyramid_emulated import HostStore, _check
-from test_sparse_align_emulated import run_emulated
 
 
 @pytest.fixture(scope="module")
@@ -62,32 +61,33 @@ def test_fast_on_any_shape(emu, oracle, w, h, levels, cell):
 
 
 @pytest.fixture(scope="module")
-def emu_reference_width():
+def k1_default():
+    return k1_emulated.Emulated(0)
+
+
+@pytest.fixture(scope="module")
+def k1_reference_width():
     """the reference-width build of K1 (emu_build.BUILDS[2]: -DSIA_F64_PARTIALS)"""
-    from emu_build import BUILDS, build_emulated
-    return build_emulated(BUILDS[2])
+    return k1_emulated.Emulated(2)
 
 
-def _sparse_align_on_a_shape(emu, oracle, shape):
-    b, (hi, lo, n_iter) = k1_width_cases.shape_case(*shape)
-    T_o, res_o, _ = run_oracle(oracle, b, hi, lo)
-    T_h, ntr, iters, H, status = run_emulated(emu, b, hi, lo)
-    assert se3.log_norm(T_h, T_o).max() <= 1e-4
-    assert np.array_equal(ntr, np.array([r["n_tracked"] for r in res_o]))
+def _sparse_align_on_a_shape(backend, oracle, w, h, n):
+    c = k1.case(f"shape_{w}x{h}_n{n}")
+    k1.verify_pair(oracle, backend.name, c.name, c.schedules[0], backend.run(c, c.schedules[0]))
 
 
-@pytest.mark.parametrize("w,h,n,levels,lo,hi", k1_width_cases.SHAPES)
-def test_sparse_align_on_any_shape(emu, oracle, w, h, n, levels, lo, hi):
+@pytest.mark.parametrize("w,h,n,levels,lo,hi", k1.SHAPES)
+def test_sparse_align_on_any_shape(k1_default, oracle, w, h, n, levels, lo, hi):
     """(64-, 128-, 256-, 512- and 1024-lane workgroups; a frame with a third of the patches in the middle of the batch -- 513 of
     520 for the 1024-lane one, so that it stays above 512)"""
-    _sparse_align_on_a_shape(emu, oracle, (w, h, n, levels, lo, hi))
+    _sparse_align_on_a_shape(k1_default, oracle, w, h, n)
 
 
-@pytest.mark.parametrize("w,h,n,levels,lo,hi", k1_width_cases.SHAPES)
-def test_sparse_align_on_any_shape_at_reference_width(emu_reference_width, oracle, w, h, n, levels, lo, hi):
+@pytest.mark.parametrize("w,h,n,levels,lo,hi", k1.SHAPES)
+def test_sparse_align_on_any_shape_at_reference_width(k1_reference_width, oracle, w, h, n, levels, lo, hi):
     """the same shapes and asserts on the -DSIA_F64_PARTIALS build: f64 products and SE3::exp, the scalar pixel loop, in every
     workgroup size"""
-    _sparse_align_on_a_shape(emu_reference_width, oracle, (w, h, n, levels, lo, hi))
+    _sparse_align_on_a_shape(k1_reference_width, oracle, w, h, n)
 
 
 @pytest.mark.parametrize("kind", ["pinhole", "atan"])

@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 import torch
 
-from rpg_svo_amd import se3, synth
-
-from helpers import make_batch, run_hip, run_oracle
+import k1_cases as k1
+import k1_device
+from helpers import make_batch, run_hip
+from rpg_svo_amd import se3
 
 pytestmark = pytest.mark.gpu
 
@@ -18,10 +19,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def big_vga(gpu_device):
     """configs[1] at bench scale: 2048 replay pairs, 640x480, 4 levels, 200 patches."""
-    seq = synth.make_sequence(2049, 200, device=gpu_device)
-    seq.images = seq.images.cpu()
-    seq.px, seq.f, seq.pos = seq.px.cpu(), seq.f.cpu(), seq.pos.cpu()
-    return seq
+    return k1.seq_bench(gpu_device)
 
 
 def test_config1_bench_scale_properties(oracle, gpu_device, big_vga, checker):
@@ -41,10 +39,9 @@ def test_config1_bench_scale_properties(oracle, gpu_device, big_vga, checker):
         Ti, outi, _ = run_hip(bi, 3, 0)
         assert np.array_equal(Ti[0], T1[i]) and torch.equal(outi.iters[0], out1.iters[i])
     # (4) oracle parity on a bounded sample of the same launch
-    S = 64
-    bs = make_batch(big_vga, [(i, i + 1) for i in range(0, B, B // S)], 4)
-    To, _, _ = run_oracle(oracle, bs, 3, 0, which=checker)
-    assert se3.log_norm(T1[:: B // S], To).max() <= 1e-4
+    sample = k1.case("config1_sample")
+    sample.built(seq=big_vga)
+    k1.verify_pair(oracle, k1.DEV, sample.name, sample.schedules[0], k1_device.answer(T1, out1).rows(slice(None, None, 32)), which=checker)
 
 
 def test_patch_order_invariance(gpu_device, big_vga):
@@ -72,42 +69,25 @@ def test_zero_motion_fixed_point_at_scale(gpu_device, big_vga):
 
 def test_config3_xga5_n1000_parity(oracle, gpu_device, checker):
     """configs[3] shape: 1280x960, 5 levels (4->0), 1000 patches per frame (1024-lane workgroups)."""
-    cam = synth.Camera(1280, 960, 800.0, 800.0, 640.0, 480.0)
-    seq = synth.make_sequence(9, 1000, cam=cam, seed=3, margin=56, cell=32, device=gpu_device)
-    seq.images = seq.images.cpu(); seq.px, seq.f, seq.pos = seq.px.cpu(), seq.f.cpu(), seq.pos.cpu()
-    b = make_batch(seq, [(i, i + 1) for i in range(8)], 5)
-    # ragged frames: the split kernel's third part partly filled and its fourth empty; points missing in a stripe
-    b.n[2] = 700
-    b.n[5] = 513
-    b.has_point[6, 100:400:3] = 0
-    To, res_o, _ = run_oracle(oracle, b, 4, 0, which=checker)
-    # Round 6: svo_hip_sparse_align splits such a frame (> 512 patches, a batch of <= 128 frames) over FOUR workgroups of 256
+    c = k1.case("config3")
+    b, schedule = c.built(device=gpu_device)[0], c.schedules[0]
+    # svo_hip_sparse_align splits such a frame (> 512 patches, a batch of <= 128 frames) over FOUR workgroups of 256
     # lanes on one XCD that exchange their sums through its L2; svo_hip_sparse_align_workgroup keeps the frame on one
     # workgroup of 1024 lanes.  Both against the checker, and against each other: the same iteration counts and tracked
     # patches, poses to rounding (the sums are formed in a different order).
-    Th, out, _ = run_hip(b, 4, 0)
-    Tw, out_w, _ = run_hip(b, 4, 0, kernel="workgroup")
-    for T, o in ((Th, out), (Tw, out_w)):
-        d = se3.log_norm(T, To)
-        assert d.max() <= 1e-4 and np.median(d) <= 2e-6
-        assert np.array_equal(o.n_tracked.cpu().numpy(), np.array([r["n_tracked"] for r in res_o]))
-        assert (o.status.cpu().numpy() == 0).all()
-    assert se3.log_norm(Th, b.T_gt_w)[[0, 1, 3, 4, 7]].max() < 5e-4
-    assert se3.log_norm(Th, Tw).max() < 1e-7
-    it_s, it_w = out.iters.cpu().numpy(), out_w.iters.cpu().numpy()
-    assert (it_s != it_w).any(axis=1).sum() <= 1  # (a stop decision on an f32 chi2 a rounding apart, at most)
+    split, one = k1_device.run(c, schedule), k1_device.run(c, schedule, "workgroup")
+    for backend, answer in ((k1.DEV, split), (k1.DEV_WG, one)):
+        k1.verify_pair(oracle, backend, c.name, schedule, answer, which=checker)
+        assert (answer.status == 0).all()
+    assert se3.log_norm(split.pose, b.T_gt_w)[[0, 1, 3, 4, 7]].max() < 5e-4
+    k1.verify_split(split, one)
 
 
 def test_config4_rig_752_default_schedule_parity(oracle, gpu_device, checker):
     """configs[4] shape: 752x480 cameras, reference default schedule (levels 4->2), 64 frames."""
-    cam = synth.Camera(752, 480, 315.5, 315.5, 376.0, 240.0)
-    seq = synth.make_sequence(65, 120, cam=cam, seed=11, margin=56, cell=40, device=gpu_device)
-    seq.images = seq.images.cpu(); seq.px, seq.f, seq.pos = seq.px.cpu(), seq.f.cpu(), seq.pos.cpu()
-    b = make_batch(seq, [(i, i + 1) for i in range(64)], 5)
-    To, res_o, _ = run_oracle(oracle, b, 4, 2, n_threads=8, which=checker)
-    Th, out, _ = run_hip(b, 4, 2)
-    d = se3.log_norm(Th, To)
-    assert d.max() <= 1e-4 and np.median(d) <= 1e-5
+    c = k1.case("config4")
+    c.built(device=gpu_device)
+    k1.verify_pair(oracle, k1.DEV, c.name, c.schedules[0], k1_device.run(c, c.schedules[0]), which=checker)
 
 
 def test_store_beyond_4gib_addresses_correctly(gpu_device, big_vga):

@@ -1,11 +1,11 @@
 """K1 at the reference's width on the GPU: rpg_svo_amd/lib/variants/libsvo_hip_SIA_F64_PARTIALS.so -- the build of
 csrc/sparse_align.hip with the per-pixel products, the patch sums and SE3::exp in f64, the scalar pixel loop and three waves
-per SIMD, the library behind the benchmark's `roofline_f64_build` figure -- against the oracle, with the bounds
-tests/test_sparse_align_gpu.py and test_full_size_gpu.py::test_config3_xga5_n1000_parity state for the default library.
+per SIMD, the library behind the benchmark's `roofline_f64_build` figure -- against the oracle, under the device profiles of
+tests/k1_cases.py: the bounds the default library holds in tests/test_sparse_align_gpu.py and tests/test_full_size_gpu.py.
 
 rpg_svo_amd.capi binds one library per process, so ONE child process (tests/k1_width_child.py, started fresh with
-SVO_HIP_LIB set) runs every case of tests/k1_width_cases.py on the variant and leaves its arrays in a file; the tests here
-build the same cases, run the oracle (and, where noted, the default library in this process) and compare.  A missing variant,
+SVO_HIP_LIB set) runs the variant pairs of tests/k1_cases.py's table on the variant and leaves its answers in a file; the tests
+here build the same cases, run the oracle (and, where noted, the default library in this process) and apply that module's rule.  A missing variant,
 a child that exits non-zero or runs into its time limit FAILS the fixture, and with it every test of the module, before any of
 them starts something on the GPU."""
 import os
@@ -15,23 +15,15 @@ import sys
 import numpy as np
 import pytest
 
-import k1_width_cases as cases
-from helpers import run_hip, run_oracle
+import k1_cases as k1
+import k1_device
+import k1_width_child
 from rpg_svo_amd import se3
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-4
-TOL_MEDIAN = 2e-6
-MIN_SAME_ITERATIONS = 0.97   # tests/test_sparse_align_gpu.py; measured 0.995 for both widths on 8192 frames (profiles/r05b_k1_width_ab.txt)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANT = os.path.join(ROOT, "rpg_svo_amd", "lib", "variants", "libsvo_hip_SIA_F64_PARTIALS.so")
-FIELDS = ("pose", "iters", "n_tracked", "status", "H", "chi2")
-
-# Ten times the largest distance of the variant's single step to the oracle measured on an MI355X (both levels, both
-# checkers: the figures in test_single_step's docstring); below 1e-6 whatever is measured.
-SINGLE_STEP_BOUND_GPU = 5.66e-8
-
 
 _child = {}   # "arrays" or "failure": the child runs ONCE per session, whatever pytest does with the fixture
 
@@ -52,194 +44,130 @@ def _run_child(out):
     return None
 
 
+class Variant:
+    """the child's answers as a backend: run(case, schedule, kernel) -> K1Answer, kernel "auto", "workgroup" or "again" (the
+    second run of k1_cases.VAR_TWICE)"""
+
+    def __init__(self, arrays):
+        self.arrays = arrays
+
+    def run(self, case, schedule, kernel="auto"):
+        return k1.K1Answer(**{f: self.arrays[k1_width_child.key(case.name, schedule, kernel) + f] for f in k1.FIELDS})
+
+
 @pytest.fixture(scope="module")
 def variant(gpu_device, tmp_path_factory):
-    """the child's arrays: "<case>/<auto|workgroup|again>/<field>"; fails (never skips) without them"""
+    """the child's answers; fails (never skips) without them"""
     if not _child:
         _child["failure"] = _run_child(str(tmp_path_factory.mktemp("k1_width") / "variant.npz"))
     if _child["failure"]:
         pytest.fail(_child["failure"])
     assert str(_child["arrays"]["lib_path"]) == VARIANT
-    return _child["arrays"]
+    return Variant(_child["arrays"])
 
 
-_built, _oracle, _default = {}, {}, {}
-
-
-def case(name):
-    if name not in _built:
-        _built[name] = cases.CASES[name]()
-    return _built[name]
-
-
-def oracle_of(oracle, name, which):
-    """(T, res) of the checker on a case: computed once, shared by the tests and left alone"""
-    if (name, which) not in _oracle:
-        b, (hi, lo, n_iter) = case(name)
-        if name == "wave1024":   # 32 different problems, 32 times over
-            import copy
-            b32 = copy.copy(b)
-            for k in ("ref_slot", "cur_slot", "T_ref_w", "T_gt_w", "T_cur_w", "px", "f", "pos", "n", "has_point"):
-                setattr(b32, k, getattr(b, k)[:32])
-            b = b32
-        T, res, _ = run_oracle(oracle, b, hi, lo, n_iter, which=which)
-        _oracle[(name, which)] = (T, res)
-    return _oracle[(name, which)]
+_default = {}
 
 
 def default_of(name):
     """the default library (this process's) on a case"""
     if name not in _default:
-        b, (hi, lo, n_iter) = case(name)
-        T, out, _ = run_hip(b, hi, lo, n_iter)
-        _default[name] = dict(pose=T, **{f: getattr(out, f).cpu().numpy() for f in FIELDS[1:]})
+        _default[name] = k1_device.run(k1.case(name), k1.case(name).schedules[0])
     return _default[name]
 
 
-def got(variant, name, kernel="auto"):
-    return {f: variant[f"{name}/{kernel}/{f}"] for f in FIELDS}
+def run_and_verify(variant, oracle, checker, name, schedule=None, kernel="auto"):
+    """-> (the case, the variant's answer, what the rule measured)"""
+    c = k1.case(name)
+    schedule = schedule or c.schedules[0]
+    answer = variant.run(c, schedule, kernel)
+    backend = k1.VAR_WG if kernel == "workgroup" else k1.VAR
+    return c, answer, k1.verify_pair(oracle, backend, name, schedule, answer, which=checker)
 
 
-def compare(variant, oracle, name, which, kernel="auto", tol=TOL, rows=slice(None)):
-    """tests/test_sparse_align_gpu.py::compare on the child's arrays"""
-    T_o, res_o = oracle_of(oracle, name, which)
-    g = {f: a[rows] for f, a in got(variant, name, kernel).items()}
-    d = se3.log_norm(g["pose"], T_o)
-    assert np.all(np.isfinite(g["pose"]))
-    assert d.max() <= tol, f"max SE3 log-norm {d.max():.3e} (argmax {d.argmax()})"
-    same = np.all(np.array([r["iters"] for r in res_o]) == g["iters"], axis=1)
-    assert np.array_equal(g["n_tracked"][same], np.array([r["n_tracked"] for r in res_o])[same])
-    assert np.array_equal(g["status"], np.array([r["stop"] for r in res_o]))
-    return d, same, res_o, g
-
-
-def split_against_one_workgroup(variant, name):
-    a, w = got(variant, name, "auto"), got(variant, name, "workgroup")
-    assert se3.log_norm(a["pose"], w["pose"]).max() < 1e-7
-    assert (a["iters"] != w["iters"]).any(axis=1).sum() <= 1
-
-
-@pytest.mark.parametrize("shape", cases.SHAPE_IDS)
+@pytest.mark.parametrize("shape", k1.SHAPE_IDS)
 def test_every_workgroup_size(variant, oracle, checker, shape):
     """64-, 128-, 256-, 512- and 1024-lane workgroups of the reference-width build on odd image sizes, the middle frame ragged;
     the 520-patch frames split over four workgroups (svo_hip_sparse_align) and on one of 1024 lanes
     (svo_hip_sparse_align_workgroup), each against the checker and against each other"""
     name = "shape_" + shape
-    for kernel in ("auto", "workgroup") if name in cases.WORKGROUP_TOO else ("auto",):
-        d, same, res_o, g = compare(variant, oracle, name, checker, kernel)
-        assert (~same).sum() <= 1
-        if name in cases.WORKGROUP_TOO:   # (the median test_config3_xga5_n1000_parity states for the 1024-lane frames)
-            assert np.median(d) <= TOL_MEDIAN
-    if name in cases.WORKGROUP_TOO:
-        split_against_one_workgroup(variant, name)
+    answers = {kernel: run_and_verify(variant, oracle, checker, name, kernel=kernel)[1]
+               for kernel in (("auto", "workgroup") if name in k1.WORKGROUP_TOO else ("auto",))}
+    if name in k1.WORKGROUP_TOO:
+        k1.verify_split(answers["auto"], answers["workgroup"])
 
 
 def test_benchmark_instantiation(variant, oracle, checker):
     """sia_kernel<256, true, false>, VGA, 200 patches, levels 3 -> 0 (test_config2_vga_4levels)"""
-    d, same, res_o, g = compare(variant, oracle, "vga16", checker)
-    b, _ = case("vga16")
-    assert np.median(d) <= TOL_MEDIAN
-    assert (~same).sum() <= 1, f"{(~same).sum()} of {len(same)} problems ran different iteration counts"
-    assert se3.log_norm(g["pose"], b.T_gt_w).max() < 5e-4
-    Ho = np.stack([r["H"] for r in res_o])[same]
-    assert np.allclose(g["H"].reshape(-1, 6, 6)[same], Ho, rtol=1e-5, atol=1e-3 * np.abs(Ho).max())
-    assert np.allclose(g["chi2"][same], np.array([r["chi2"] for r in res_o])[same], rtol=1e-4)
+    c, answer, m = run_and_verify(variant, oracle, checker, "vga16")
+    assert se3.log_norm(answer.pose, c.batch.T_gt_w).max() < 5e-4
 
 
 def test_variant_is_another_build_and_repeats_itself(variant):
     """the child did not run the default library under another name: on the 16 VGA pairs its poses differ in their bits from
     this process's default library, within the tolerance both hold against the oracle; and run twice it gives the same bits"""
-    v, dflt = got(variant, "vga16"), default_of("vga16")
-    assert not np.array_equal(v["pose"].view(np.uint64), dflt["pose"].view(np.uint64))
-    assert se3.log_norm(v["pose"], dflt["pose"]).max() <= TOL
-    again = got(variant, "vga16", "again")
-    for f in FIELDS:
-        assert np.array_equal(v[f].view(np.uint8), again[f].view(np.uint8)), f
+    c = k1.case("vga16")
+    v, dflt = variant.run(c, c.schedules[0]), default_of("vga16")
+    assert not np.array_equal(v.pose.view(np.uint64), dflt.pose.view(np.uint64))
+    assert se3.log_norm(v.pose, dflt.pose).max() <= k1.DEVICE.max_d
+    again = variant.run(c, c.schedules[0], "again")
+    for f in k1.FIELDS:
+        assert np.array_equal(getattr(v, f).view(np.uint8), getattr(again, f).view(np.uint8)), f
 
 
 @pytest.mark.parametrize("name", ["radtan_4to2", "radtan_3to0", "atan_4to2", "atan_3to0"])
 def test_distorted_cameras(variant, oracle, checker, name):
-    """the DIST instantiations, with the asserts of test_sparse_align_gpu.py::test_distorted_camera_models (which states no
+    """the DIST instantiations, with the bounds of test_sparse_align_gpu.py::test_distorted_camera_models (which states no
     bound on the iteration sequences: under radtan the emulated kernels of BOTH widths part from the oracle's sequence by one
     last evaluation on one or two of these five frames, poses within 5e-6)"""
-    d, same, res_o, g = compare(variant, oracle, name, checker)
-    assert np.median(d) <= (1e-5 if name.endswith("4to2") else TOL_MEDIAN)
-    if name.endswith("3to0"):
-        assert se3.log_norm(g["pose"], case(name)[0].T_gt_w).max() < 1e-3   # both solved the problem
+    kind, levels = name.split("_")
+    schedule = {"4to2": (4, 2, 30), "3to0": (3, 0, 30)}[levels]
+    c, answer, m = run_and_verify(variant, oracle, checker, f"{kind}_120", schedule)
+    if levels == "3to0":
+        assert se3.log_norm(answer.pose, c.batch.T_gt_w).max() < 1e-3   # both solved the problem
 
 
 def test_distorted_camera_on_520_patches(variant, oracle, checker):
-    """sia_kernel<256, false, true, 4> (svo_hip_sparse_align splits the frame) and sia_kernel<1024, false, true>, with the
-    asserts of test_config3_xga5_n1000_parity: each against the checker, and against each other"""
-    for kernel in ("auto", "workgroup"):
-        d, same, res_o, g = compare(variant, oracle, "atan_520", checker, kernel)
-        assert np.median(d) <= TOL_MEDIAN
-        assert (~same).sum() <= 1
-    split_against_one_workgroup(variant, "atan_520")
+    """sia_kernel<256, false, true, 4> (svo_hip_sparse_align splits the frame) and sia_kernel<1024, false, true>, under the
+    bounds of test_config3_xga5_n1000_parity: each against the checker, and against each other"""
+    answers = {kernel: run_and_verify(variant, oracle, checker, "atan_520", kernel=kernel)[1] for kernel in ("auto", "workgroup")}
+    k1.verify_split(answers["auto"], answers["workgroup"])
 
 
 def test_ragged_and_missing_points(variant, oracle, checker):
-    """test_sparse_align_gpu.py::test_ragged_and_missing_points: n = 200, 12, 64, 65, 137, 0, 1"""
-    b, _ = case("ragged")
-    T_o, res_o = oracle_of(oracle, "ragged", checker)
-    g = got(variant, "ragged")
-    d = se3.log_norm(g["pose"], T_o)
-    assert g["n_tracked"][5] == 0 and res_o[5]["n_tracked"] == 0
-    assert np.allclose(g["pose"][5], b.T_cur_w[5], atol=1e-15)
-    assert d[[0, 2, 3, 4]].max() <= TOL, d
-    assert d[1] <= 1e-3, d
-    assert np.all(np.isfinite(g["pose"][6])) and g["n_tracked"][6] <= 1
+    """n = 200, 12, 64, 65, 137, 0, 1"""
+    c = k1.case("ragged")
+    k1.verify_ragged(oracle, k1.VAR, variant.run(c, c.schedules[0]), which=checker)
 
 
 def test_border_features_and_visibility(variant, oracle, checker):
-    compare(variant, oracle, "border_3to0", checker)
-    d, same, res_o, g = compare(variant, oracle, "border_3to2", checker)
-    assert np.all(g["n_tracked"] < 200) and np.all(g["n_tracked"] > 100), g["n_tracked"]
+    for schedule in k1.case("border").schedules:
+        c, answer, m = run_and_verify(variant, oracle, checker, "border", schedule)
+    assert np.all(answer.n_tracked < 200) and np.all(answer.n_tracked > 100), answer.n_tracked
 
 
 def test_all_patches_outside(variant, oracle, checker):
-    T_o, res_o = oracle_of(oracle, "outside", checker)
-    g = got(variant, "outside")
-    assert res_o[0]["n_tracked"] == 0 and g["n_tracked"][0] == 0
-    assert se3.log_norm(g["pose"][:1], T_o[:1]).max() < 1e-12
-    assert se3.log_norm(g["pose"][1:], T_o[1:]).max() <= TOL
+    c = k1.case("outside")
+    k1.verify_outside(oracle, k1.VAR, "outside", variant.run(c, c.schedules[0]), which=checker)
 
 
 @pytest.mark.parametrize("n_iter", [0, 1, 2])
 def test_iteration_caps(variant, oracle, checker, n_iter):
-    T_o, res_o = oracle_of(oracle, f"itercap_{n_iter}", checker)
-    g = got(variant, f"itercap_{n_iter}")
-    assert se3.log_norm(g["pose"], T_o).max() <= 1e-6
-    assert np.array_equal(g["iters"], np.array([r["iters"] for r in res_o]))
-    assert np.array_equal(g["n_tracked"], np.array([r["n_tracked"] for r in res_o]))
+    run_and_verify(variant, oracle, checker, "itercap", (3, 0, n_iter))
 
 
 def test_iteration_counts_on_256_problems(variant, oracle, checker):
     """16 pairs x 16 priors: >= 97 % identical per-level iteration sequences (the condition of
     test_iteration_counts_on_a_large_sample), tracked counts equal on those, every pose within 1e-4"""
-    d, same, res_o, g = compare(variant, oracle, "sample256", checker)
-    print(f"identical iteration sequences: {same.mean():.4f} of {len(same)}; median distance {np.median(d):.3e}")
-    assert same.mean() >= MIN_SAME_ITERATIONS, f"only {same.mean():.4f} of {len(same)} problems ran identical iteration counts"
-    assert np.median(d) <= TOL_MEDIAN
+    run_and_verify(variant, oracle, checker, "sample256")
 
 
 @pytest.mark.parametrize("level", [3, 0])
 def test_single_step(variant, oracle, checker, level):
     """ONE Gauss-Newton step at one level from a prior 5e-3 off (tests/test_sparse_align_emulated.py::
-    test_emulated_single_gauss_newton_step): the f64 se3_exp and the products with nothing to correct them afterwards.
-    Measured on an MI355X, max over the 12 frames, against either checker: level 3 5.658e-09, level 0 2.142e-09 (the figures
-    of the emulated reference-width build, digit for digit).  SINGLE_STEP_BOUND_GPU is the larger one times 10."""
-    name = f"step_level{level}"
-    T_o, res_o = oracle_of(oracle, name, checker)
-    g = got(variant, name)
-    d = se3.log_norm(g["pose"], T_o)
-    print(f"single step at level {level} against {checker}: max distance {d.max():.3e}")
-    assert np.array_equal(g["iters"], np.array([r["iters"] for r in res_o]))
-    assert np.array_equal(g["n_tracked"], np.array([r["n_tracked"] for r in res_o]))
-    Ho = np.array([np.asarray(r["H"]).ravel() for r in res_o])
-    assert np.abs(g["H"].reshape(-1, 36) - Ho).max() <= 1e-4 * np.abs(Ho).max()
-    assert SINGLE_STEP_BOUND_GPU < 1e-6
-    assert d.max() <= SINGLE_STEP_BOUND_GPU, d
+    test_emulated_single_gauss_newton_step): the f64 se3_exp and the products with nothing to correct them afterwards, to
+    k1_cases.SINGLE_STEP_BOUND_GPU (with the figures it comes from)"""
+    run_and_verify(variant, oracle, checker, f"step_level{level}")
 
 
 def test_wave_kernel_is_the_same_code_in_both_libraries(variant, oracle, checker):
@@ -247,10 +175,9 @@ def test_wave_kernel_is_the_same_code_in_both_libraries(variant, oracle, checker
     wave-per-frame kernel in the reference-width library too (the benchmark's 200-patch headline does not take that path).
     Pinned down: on 32 pairs x 60 patches tiled to B = 1024 the variant's poses, iteration counts and H are the default
     library's bit for bit -- and hold the wave kernel's bounds against the checker."""
-    v, dflt = got(variant, "wave1024"), default_of("wave1024")
+    c = k1.case("wave1024")
+    v, dflt = variant.run(c, c.schedules[0]), default_of("wave1024")
     for f in ("pose", "iters", "H"):
-        assert np.array_equal(v[f].view(np.uint8), dflt[f].view(np.uint8)), f
-    assert np.array_equal(v["pose"].reshape(32, 32, 12), np.broadcast_to(v["pose"][:32], (32, 32, 12)))
-    d, same, res_o, g = compare(variant, oracle, "wave1024", checker, rows=slice(0, 32))
-    assert np.median(d) <= TOL_MEDIAN
-    assert (~same).sum() <= 1
+        assert np.array_equal(getattr(v, f).view(np.uint8), getattr(dflt, f).view(np.uint8)), f
+    assert np.array_equal(v.pose.reshape(32, 32, 12), np.broadcast_to(v.pose[:32], (32, 32, 12)))
+    run_and_verify(variant, oracle, checker, "wave1024")
