@@ -595,6 +595,20 @@ int svo_hip_pose_optimize_deferred(const svo_hip_camera* cam, int B, const int32
                                    uint8_t* d_has_point, double reproj_thresh, int n_iter, double* d_T_f_w,
                                    double* d_Cov, double* d_stats, int32_t* d_ran, void* stream);
 
+/* svo_hip_pose_optimize for a caller whose flags and poses live in buffers it wants to keep (a result block reused from
+ * step to step): d_has_point_in [B][n_stride] and d_T_in [B][12] are only read, d_has_point_out and d_T_out only written.
+ * Contract: d_has_point_out, d_T_out, d_Cov, d_stats and d_ran end up byte for byte as after copying d_has_point_in to
+ * d_has_point_out and d_T_in to d_T_out and calling svo_hip_pose_optimize on the copies -- every byte of every row, the
+ * slots at and beyond d_n[b] included, and every kind of frame: d_n[b] <= 0, no observation with a point (d_ran 0: the pose
+ * and the flags as they came in), frames the wave kernel hands to the ordered kernel, n_iter == 0, n_stride > 256 (the
+ * ordered kernel works in place: this one case does copy).  No copy kernel runs otherwise: the wave kernel reads every flag
+ * and the pose anyway and carries them over.  d_has_point_out == d_has_point_in and d_T_out == d_T_in (each on its own) are
+ * allowed and mean in place, exactly svo_hip_pose_optimize; buffers that overlap in any other way are not. */
+int svo_hip_pose_optimize_into(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride, const double* d_f,
+                               const int32_t* d_level, const double* d_pos, const uint8_t* d_has_point_in,
+                               const double* d_T_in, double reproj_thresh, int n_iter, uint8_t* d_has_point_out,
+                               double* d_T_out, double* d_Cov, double* d_stats, int32_t* d_ran, void* stream);
+
 /*
  * K6: batched Point::optimize (svo/src/point.cpp:119-177).  Point p has observations
  * [d_obs_ptr[p], d_obs_ptr[p+1]) in (d_obs_frame -> frame table, d_obs_f); d_pos in/out.

@@ -13,9 +13,9 @@
 // Lane 0 runs the 6x6 pivoted LDLT (Eigen's algorithm), the rollback / convergence rules
 // and SE3::exp(dT)*T; medians are found by exact rank counting in LDS (nth_element's value).
 //
-// Entry points: svo_hip_pose_optimize, _deferred and _ordered are one-line calls of pose_optimize_impl with a mode; it checks the
-// arguments, fills one svo_track::PoseWaveArgs and hands it to the wave kernel (pose_optimizer_wave.hip) and / or to
-// launch_ordered, which builds this file's PoseArgs from it.
+// Entry points: svo_hip_pose_optimize, _deferred and _ordered (in place) and svo_hip_pose_optimize_into (inputs read where they
+// are) are one-line calls of pose_optimize_impl with a mode; it checks the arguments, fills one svo_track::PoseWaveArgs and hands
+// it to the wave kernel (pose_optimizer_wave.hip) and / or to launch_ordered, which builds this file's PoseArgs from it.
 #pragma clang fp contract(off)
 #include "track_kernels.h"
 #include "track_math.h"
@@ -28,6 +28,7 @@ namespace {
 constexpr int PO_MINW = 4;
 constexpr int PO_HALF = 32;
 constexpr int PO_BLOCK = 64;  // one wave per frame: the serial parts dominate, occupancy comes from many small workgroups
+static_assert(PO_BLOCK == 64, "pose_opt_flagged_kernel finds its frames with one ballot over the workgroup");
 constexpr int PO_MAXN = 1024;
 constexpr double SVO_EPS = 0.0000000001;  // svo/include/svo/global.h:77
 
@@ -45,7 +46,7 @@ struct PoseArgs {
   double* Cov;
   double* stats;
   int32_t* ran;
-  int only_flagged;  // 1: work only on frames the wave kernel handed over (ran[b] == 2)
+  int B;  // frames (the scan of pose_opt_flagged_kernel stops there)
 };
 
 struct PoseLds {
@@ -102,17 +103,9 @@ struct PoseDyn {
   uint8_t* hp;
 };
 
-__global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_kernel(const PoseArgs a) {
-  __shared__ PoseLds s;
-  SVO_DYNAMIC_LDS(double, po_dyn);
-  const int ns8 = (a.n_stride + 7) & ~7;
-  PoseDyn d;
-  d.vals = po_dyn;
-  d.err = reinterpret_cast<float*>(po_dyn + ns8);
-  d.hp = reinterpret_cast<uint8_t*>(d.err + ns8);
-  const int b = blockIdx.x;
+// Frame b, in place on a.T / a.has_point, by the PO_BLOCK lanes of the workgroup (all of them call it, with the same b).
+__device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, PoseLds& s, const PoseDyn& d) {
   const int tid = threadIdx.x;
-  if (a.only_flagged && a.ran[b] != 2) return;
   int n = a.n[b];
   n = n < 0 ? 0 : (n > a.n_stride ? a.n_stride : n);  // contract: n <= n_stride; never index past the row
   const size_t base = (size_t)b * a.n_stride;
@@ -379,6 +372,41 @@ __global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_kernel(const PoseA
   }
 }
 
+__device__ __forceinline__ PoseDyn pose_dyn(double* po_dyn, int n_stride) {
+  const int ns8 = (n_stride + 7) & ~7;
+  PoseDyn d;
+  d.vals = po_dyn;
+  d.err = reinterpret_cast<float*>(po_dyn + ns8);
+  d.hp = reinterpret_cast<uint8_t*>(d.err + ns8);
+  return d;
+}
+
+// Every frame: one workgroup each.
+__global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_kernel(const PoseArgs a) {
+  __shared__ PoseLds s;
+  SVO_DYNAMIC_LDS(double, po_dyn);
+  pose_opt_frame(a, blockIdx.x, s, pose_dyn(po_dyn, a.n_stride));
+}
+
+// The frames the wave kernel handed over (ran[b] == 2) alone: one workgroup per PO_BLOCK frames reads their PO_BLOCK words of
+// `ran` at once and runs the flagged ones one after the other, in ascending order.  Frames do not depend on each other, so
+// a frame's result is what a workgroup of its own gives; a batch without a flagged frame -- the usual one -- costs B / 64
+// workgroups of one load each instead of B.
+__global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_flagged_kernel(const PoseArgs a) {
+  __shared__ PoseLds s;
+  SVO_DYNAMIC_LDS(double, po_dyn);
+  const PoseDyn d = pose_dyn(po_dyn, a.n_stride);
+  const int b0 = blockIdx.x * PO_BLOCK;
+  const int mine = b0 + (int)threadIdx.x;
+  unsigned long long todo = __ballot(mine < a.B && a.ran[mine] == 2);  // (read before any frame of this chunk writes its word)
+  while (todo) {
+    const int k = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    pose_opt_frame(a, b0 + k, s, d);
+    __syncthreads();  // the next frame starts over on s and d
+  }
+}
+
 }  // namespace
 
 // The ordered kernel on the frames of `w`; only_flagged = 1: on those the wave kernel handed over (ran = 2) alone.
@@ -397,10 +425,13 @@ static int launch_ordered(const svo_track::PoseWaveArgs& w, int only_flagged, hi
   a.Cov = w.Cov;
   a.stats = w.stats;
   a.ran = w.ran;
-  a.only_flagged = only_flagged;
+  a.B = w.B;
   const int ns8 = (w.n_stride + 7) & ~7;
   const size_t dyn = (size_t)ns8 * (sizeof(double) + sizeof(float) + 1);
-  hipLaunchKernelGGL(pose_opt_kernel, dim3(w.B), dim3(PO_BLOCK), dyn, s, a);
+  if (only_flagged)
+    hipLaunchKernelGGL(pose_opt_flagged_kernel, dim3((w.B + PO_BLOCK - 1) / PO_BLOCK), dim3(PO_BLOCK), dyn, s, a);
+  else
+    hipLaunchKernelGGL(pose_opt_kernel, dim3(w.B), dim3(PO_BLOCK), dyn, s, a);
   return check_launch();
 }
 
@@ -410,13 +441,16 @@ enum PoseMode { POSE_WAVE_FINISH, POSE_WAVE_DEFERRED, POSE_ORDERED };
 
 // The three entries: one check of the arguments (scalars: EINVAL; n_stride beyond the kernels: ERANGE; the empty batch: OK;
 // the arrays: EINVAL -- in this order), one argument block, one dispatch.
+// d_has_point_in / d_T_in: where the flags and the poses are read; the same pointers as d_has_point / d_T_f_w: in place.
 static int pose_optimize_impl(PoseMode mode, const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride, const double* d_f,
-                              const int32_t* d_level, const double* d_pos, uint8_t* d_has_point, double reproj_thresh,
-                              int n_iter, double* d_T_f_w, double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
+                              const int32_t* d_level, const double* d_pos, const uint8_t* d_has_point_in, uint8_t* d_has_point,
+                              double reproj_thresh, int n_iter, const double* d_T_in, double* d_T_f_w, double* d_Cov,
+                              double* d_stats, int32_t* d_ran, void* stream) {
   if (!cam || !cam_model_ok(cam) || B < 0 || n_stride < 1 || n_iter < 0) return SVO_HIP_EINVAL;
   if (n_stride > PO_MAXN) return SVO_HIP_ERANGE;
   if (B == 0) return SVO_HIP_OK;
-  if (!d_n || !d_f || !d_level || !d_pos || !d_has_point || !d_T_f_w || !d_stats || !d_ran) return SVO_HIP_EINVAL;
+  if (!d_n || !d_f || !d_level || !d_pos || !d_has_point_in || !d_has_point || !d_T_in || !d_T_f_w || !d_stats || !d_ran)
+    return SVO_HIP_EINVAL;
   svo_track::PoseWaveArgs w;
   w.cam = *cam;
   w.B = B;
@@ -425,20 +459,27 @@ static int pose_optimize_impl(PoseMode mode, const svo_hip_camera* cam, int B, c
   w.f = d_f;
   w.level = d_level;
   w.pos = d_pos;
+  w.has_point_in = d_has_point_in;
   w.has_point = d_has_point;
   w.reproj_thresh = reproj_thresh;
   w.n_iter = n_iter;
+  w.T_in = d_T_in;
   w.T = d_T_f_w;
   w.Cov = d_Cov;
   w.stats = d_stats;
   w.ran = d_ran;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == POSE_ORDERED || n_stride > svo_track::POSE_WAVE_MAX_STRIDE)  // (more than 4 trips of 64 observations: ordered kernel)
+  if (mode == POSE_ORDERED || n_stride > svo_track::POSE_WAVE_MAX_STRIDE) {  // (more than 4 trips of 64 observations: ordered kernel)
+    // the ordered kernel works in place: rows this wide are the one case in which the inputs are copied first
+    if (d_has_point_in != d_has_point)
+      SVO_HIP_TRY(hipMemcpyAsync(d_has_point, d_has_point_in, (size_t)B * n_stride, hipMemcpyDeviceToDevice, s));
+    if (d_T_in != d_T_f_w) SVO_HIP_TRY(hipMemcpyAsync(d_T_f_w, d_T_in, (size_t)B * 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
     return launch_ordered(w, 0, s);
+  }
   const int rc = svo_track::launch_pose_wave(w, s);
   if (rc != SVO_HIP_OK || mode == POSE_WAVE_DEFERRED) return rc;
-  // frames whose normal equations are (nearly) singular were left untouched and flagged ran = 2:
-  // the ordered kernel takes exactly those (its other workgroups exit at once)
+  // frames whose normal equations are (nearly) singular were handed over with ran = 2, their flags and pose as they came in:
+  // the ordered kernel finishes exactly those, in place on the outputs (one workgroup looks at 64 frames)
   return launch_ordered(w, 1, s);
 }
 
@@ -446,22 +487,33 @@ extern "C" int svo_hip_pose_optimize(const svo_hip_camera* cam, int B, const int
                                      const double* d_f, const int32_t* d_level, const double* d_pos,
                                      uint8_t* d_has_point, double reproj_thresh, int n_iter, double* d_T_f_w,
                                      double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
-  return pose_optimize_impl(POSE_WAVE_FINISH, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w,
-                            d_Cov, d_stats, d_ran, stream);
+  return pose_optimize_impl(POSE_WAVE_FINISH, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, d_has_point, reproj_thresh, n_iter,
+                            d_T_f_w, d_T_f_w, d_Cov, d_stats, d_ran, stream);
 }
 
 extern "C" int svo_hip_pose_optimize_deferred(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride,
                                               const double* d_f, const int32_t* d_level, const double* d_pos,
                                               uint8_t* d_has_point, double reproj_thresh, int n_iter, double* d_T_f_w,
                                               double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
-  return pose_optimize_impl(POSE_WAVE_DEFERRED, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w,
-                            d_Cov, d_stats, d_ran, stream);
+  return pose_optimize_impl(POSE_WAVE_DEFERRED, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, d_has_point, reproj_thresh, n_iter,
+                            d_T_f_w, d_T_f_w, d_Cov, d_stats, d_ran, stream);
 }
 
 extern "C" int svo_hip_pose_optimize_ordered(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride,
                                              const double* d_f, const int32_t* d_level, const double* d_pos,
                                              uint8_t* d_has_point, double reproj_thresh, int n_iter, double* d_T_f_w,
                                              double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
-  return pose_optimize_impl(POSE_ORDERED, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, reproj_thresh, n_iter, d_T_f_w,
-                            d_Cov, d_stats, d_ran, stream);
+  return pose_optimize_impl(POSE_ORDERED, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point, d_has_point, reproj_thresh, n_iter,
+                            d_T_f_w, d_T_f_w, d_Cov, d_stats, d_ran, stream);
+}
+
+// svo_hip_pose_optimize reading the flags and the poses where they are and writing them elsewhere: what copying d_has_point_in
+// to d_has_point_out and d_T_in to d_T_out and calling svo_hip_pose_optimize on the copies leaves, byte for byte, without the
+// two copies (the wave kernel reads every flag and the pose anyway).
+extern "C" int svo_hip_pose_optimize_into(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride, const double* d_f,
+                                          const int32_t* d_level, const double* d_pos, const uint8_t* d_has_point_in,
+                                          const double* d_T_in, double reproj_thresh, int n_iter, uint8_t* d_has_point_out,
+                                          double* d_T_out, double* d_Cov, double* d_stats, int32_t* d_ran, void* stream) {
+  return pose_optimize_impl(POSE_WAVE_FINISH, cam, B, d_n, n_stride, d_f, d_level, d_pos, d_has_point_in, d_has_point_out, reproj_thresh,
+                            n_iter, d_T_in, d_T_out, d_Cov, d_stats, d_ran, stream);
 }

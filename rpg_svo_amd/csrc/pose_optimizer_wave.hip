@@ -7,18 +7,21 @@
 // reference's summation order (pose_optimizer.hip, svo_hip_pose_optimize_ordered) stays as the
 // checker; this kernel is what the pipeline runs:
 //
-//   * a wave reads its row once (the flag first; f, pos, level of live slots only) and writes the LIVE observations side by
+//   * a wave reads its row once, in two round trips to memory (the flag bytes of the whole row; then f, pos, level of the live
+//     slots and the pose, all requested before the one wait), and writes the LIVE observations side by
 //     side, in index order (position = ballot + popcount of the lanes below: nothing depends on timing), into its own block
 //     of the workgroup's dynamic LDS: px py pz ux uy as f64, the level scale as f32, the slot it came from as u8 -- 45 bytes
 //     per observation, structure of arrays over n_stride (rounded up to 8) positions, 9 000 bytes per wave (= workgroup) at
 //     n_stride = 200, so that sixteen of them fit a CU's 160 KB, and a finished frame frees its block for the next workgroup at
 //     once (11 520 bytes and fourteen at n_stride = 256).  Nothing is re-read from HBM between Gauss-Newton
-//     iterations, and the observations cost no registers: 127 VGPRs, four waves per SIMD (occupancy is what hides the f64
+//     iterations, and the observations cost no registers: 121 VGPRs, no scratch, four waves per SIMD (occupancy is what hides the f64
 //     dependency chains of the solve: there is no memory access in the loop to overlap them with);
 //   * an iteration walks the block in ceil(n_live / 64) trips -- a runtime loop, so a frame of 172 live observations in a
 //     row of 200 pays three trips, not four; a lane past n_live in the last trip reads the last live record again and counts
 //     with weight 0.  The two passes around the loop (MAD scale / initial median, pruning / final median) read the same block;
-//     pruning clears has_point at the slot the record came from.  The block is the wave's alone: same-wave DS operations
+//     pruning clears has_point at the slot the record came from.  The flags and the pose are read from has_point_in / T_in
+//     and written to has_point / T, which may be the same arrays (in place) or others (svo_hip_pose_optimize_into: the first
+//     pass then carries every flag byte of the row and the pose over, so that nobody copies them beforehand).  The block is the wave's alone: same-wave DS operations
 //     execute in order, SVO_WAVE_LDS_FENCE keeps the compiler from moving the reads above the stores, and there is no barrier;
 //   * the 25 distinct non-zero f64 sums of an iteration (18 entries of A -- A(0,1) is identically zero, A(1,1) is A(0,0) and
 //     A(1,4) is -A(0,3) bit for bit --, b[6], chi2) are accumulated per lane and reduced over the wave with a TRANSPOSING
@@ -49,6 +52,7 @@ using svo_track::PoseWaveArgs;
 // the byte count of the launch follow this one number; 2 and 4 were the other two builds of
 // profiles/r08a_k4_one_frame_per_workgroup.txt (compose + K4 0.2170 ms at 4, 0.2079 at 2, 0.2002 at 1; the same bytes out).
 constexpr int PW_WAVES = 1;
+constexpr int PW_TRIPS = svo_track::POSE_WAVE_MAX_STRIDE / 64;  // trips of 64 slots a row can have
 constexpr int PW_MINW = 4;  // waves per SIMD asked of the register allocator (<= 128 VGPRs)
 constexpr double SVO_EPS = 0.0000000001;  // svo/include/svo/global.h:77
 
@@ -285,6 +289,15 @@ __device__ __forceinline__ double pw_select(const unsigned long long kd[4], int 
   return __longlong_as_double((long long)r);
 }
 
+// Every load (and store) this wave has issued so far is through: ONE wait where the compiler would place one per use, and
+// a line no load moves across.  s_waitcnt vmcnt(0) alone: expcnt 7 and lgkmcnt 15 are "do not wait" (gfx9 encoding: vmcnt in
+// bits 3:0 and 15:14, expcnt in 6:4, lgkmcnt in 11:8).  The host emulation runs its loads one after the other anyway.
+__device__ __forceinline__ void pw_loads_done() {
+#ifdef __HIP_DEVICE_COMPILE__
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
+}
+
 // The 25 sums in reduction order (two more of the 27 non-zero entries are copies: A(1,1) is the expression of A(0,0), since
 // j11 == j00, and A(1,4) is -A(0,3) bit for bit, since j14 == -j03 and rounding to nearest is symmetric):
 //   0..4   A(0,0) A(0,2) A(0,3) A(0,4) A(0,5)
@@ -295,7 +308,7 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   SVO_DYNAMIC_LDS(double, pw_dyn);
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int b = blockIdx.x * PW_WAVES + wave;
+  const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * PW_WAVES + wave);  // (the wave's: addresses off it stay in SGPRs)
   if (b >= a.B) return;
   int n = __builtin_amdgcn_readfirstlane(a.n[b]);
   n = n < 0 ? 0 : (n > a.n_stride ? a.n_stride : n);  // contract: n <= n_stride (svo_hip.h); never read past the row
@@ -308,24 +321,68 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   blk.d = pw_dyn + (size_t)wave * (blk.cap / 8) * PW_BYTES_PER_OBS;  // (cap * 45 bytes per wave: a multiple of 8)
   blk.k = reinterpret_cast<float*>(blk.d + 5 * blk.cap);
   blk.slot = reinterpret_cast<uint8_t*>(blk.k + blk.cap);
-  int n_live = 0;
-  for (int j = 0; j * 64 < n; ++j) {
+  // Not in place (svo_hip_pose_optimize_into): this pass reads every flag of the frame anyway, so it also carries the row over to
+  // the output -- all n_stride slots, those beyond n as they came in -- and every exit below leaves a pose in a.T.
+  const bool carry = a.has_point_in != a.has_point;
+  // Two round trips to memory for the whole row, not two per trip of 64 slots: every load below is unconditional (an index
+  // outside the frame is moved into the row and the answer dropped afterwards) and waited for once, by pw_loads_done, because a
+  // load that only a branch uses is moved into that branch and waited for there.  First the flag bytes of all PW_TRIPS trips ...
+  uint8_t flag[PW_TRIPS];
+#pragma unroll
+  for (int j = 0; j < PW_TRIPS; ++j) {
     const int i = j * 64 + lane;
-    const bool live = (i < n) && a.has_point[base + i] != 0;
-    const unsigned long long m = __ballot(live);
-    if (live) {
-      // position = the number of live observations before this one; < n <= cap by construction, clamped all the same
-      const int at = n_live + __popcll(m & ((1ull << lane) - 1ull));
-      const int c = at < blk.cap ? at : blk.cap - 1;
-      const double* p = a.pos + 3 * (base + i);
-      const double* f = a.f + 3 * (base + i);
-      blk.d[c] = p[0]; blk.d[blk.cap + c] = p[1]; blk.d[2 * blk.cap + c] = p[2];
-      blk.d[3 * blk.cap + c] = f[0] / f[2];  // vk::project2d(f), once
-      blk.d[4 * blk.cap + c] = f[1] / f[2];
-      blk.k[c] = pow2_inv_f32(a.level[base + i]);  // == 1.0f / (float)(1 << level), from exponent bits
-      blk.slot[c] = (uint8_t)i;
-    }
+    flag[j] = a.has_point_in[base + (i < a.n_stride ? i : a.n_stride - 1)];
+  }
+  pw_loads_done();
+  // ... then who is live and where it goes: position = the number of live observations before this one (ballot + popcount of
+  // the lanes below: nothing depends on timing); < n <= cap by construction, clamped all the same ...
+  bool live[PW_TRIPS];
+  int at[PW_TRIPS];
+  int n_live = 0;
+#pragma unroll
+  for (int j = 0; j < PW_TRIPS; ++j) {
+    live[j] = (j * 64 + lane < n) && flag[j] != 0;
+    const unsigned long long m = __ballot(live[j]);
+    const int c = n_live + __popcll(m & ((1ull << lane) - 1ull));
+    at[j] = c < blk.cap ? c : blk.cap - 1;
     n_live += __popcll(m);
+  }
+  // ... then pos, f and level of all trips (a slot that is not live asks for slot 0 of the row: one address for all such lanes) ...
+  double p[PW_TRIPS][3], f[PW_TRIPS][3];
+  int lv[PW_TRIPS];
+#pragma unroll
+  for (int j = 0; j < PW_TRIPS; ++j) {
+    const size_t src = base + (live[j] ? j * 64 + lane : 0);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[j][k] = a.pos[3 * src + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) f[j][k] = a.f[3 * src + k];
+    lv[j] = a.level[src];
+  }
+  const double t_raw = a.T_in[12 * b + (lane < 12 ? lane : 11)];  // and the pose, one of its twelve doubles per lane
+  pw_loads_done();
+  // Not in place: the pose goes to the output as it came in, here and once -- the exits that leave it alone (nothing live, a
+  // frame handed over) find it done, so that whoever works on the outputs next (the ordered kernel, the caller) finds the
+  // frame, and the last line of the Gauss-Newton loop writes over it.
+  if (a.T_in != a.T && lane < 12) a.T[12 * b + lane] = t_raw;
+  if (carry) {  // (and the flags, behind the second wait: no load waits for these stores)
+#pragma unroll
+    for (int j = 0; j < PW_TRIPS; ++j) {
+      const int i = j * 64 + lane;
+      if (i < a.n_stride) a.has_point[base + i] = flag[j];
+    }
+  }
+  // ... and the records into LDS, trip after trip.
+#pragma unroll
+  for (int j = 0; j < PW_TRIPS; ++j) {
+    if (live[j]) {
+      const int c = at[j];
+      blk.d[c] = p[j][0]; blk.d[blk.cap + c] = p[j][1]; blk.d[2 * blk.cap + c] = p[j][2];
+      blk.d[3 * blk.cap + c] = f[j][0] / f[j][2];  // vk::project2d(f), once
+      blk.d[4 * blk.cap + c] = f[j][1] / f[j][2];
+      blk.k[c] = pow2_inv_f32(lv[j]);  // == 1.0f / (float)(1 << level), from exponent bits
+      blk.slot[c] = (uint8_t)(j * 64 + lane);
+    }
   }
   if (n_live == 0) {  // errors.empty(): return before touching anything (:57-58)
     if (lane == 0) a.ran[b] = 0;
@@ -337,9 +394,14 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   const int last_pos = (n_live < blk.cap ? n_live : blk.cap) - 1;
   const int trips = (n_live + 63) >> 6;
 
-  // model, wave-uniform (every lane loads the same 12 doubles)
+  // model, wave-uniform (lanes 0 .. 11 hold the twelve doubles)
   Se3 T, T_old;
-  se3_from_Rt(a.T + 12 * b, T);
+  {
+    const double Rt[12] = {readlane_f64<0>(t_raw), readlane_f64<1>(t_raw), readlane_f64<2>(t_raw),  readlane_f64<3>(t_raw),
+                           readlane_f64<4>(t_raw), readlane_f64<5>(t_raw), readlane_f64<6>(t_raw),  readlane_f64<7>(t_raw),
+                           readlane_f64<8>(t_raw), readlane_f64<9>(t_raw), readlane_f64<10>(t_raw), readlane_f64<11>(t_raw)};
+    se3_from_Rt(Rt, T);
+  }
   uni_se3(T);
   T_old = T;
   double R[9];
@@ -446,7 +508,7 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     // collapsed pivot means a (nearly) rank-deficient system -- fewer observations than degrees
     // of freedom -- where the reference's answer is decided by the rounding of its own ordered
     // sums inside Eigen's pivoted algorithm: such a frame is handed to the ordered kernel
-    // untouched (ran = 2, nothing has been written yet).
+    // untouched (ran = 2; the outputs hold the frame's flags and pose as they came in and nothing else has been written).
     double dT[6];
     double LD[21];
     ldlt6_factor_fast(A, LD);

@@ -72,10 +72,12 @@ struct PoseWaveArgs {
   const double* f;
   const int32_t* level;
   const double* pos;
-  uint8_t* has_point;
+  const uint8_t* has_point_in;  // the flags and the pose as the caller has them; == has_point / T: in place
+  uint8_t* has_point;           // out: every byte of every row (slots >= n: as they came in)
   double reproj_thresh;
   int n_iter;
-  double* T;
+  const double* T_in;
+  double* T;                    // out: written on every exit (T_in where the kernel leaves the pose alone)
   double* Cov;
   double* stats;
   int32_t* ran;

@@ -256,7 +256,18 @@ def optimize_gauss_newton(cam, n, f, level, pos, has_point, T_f_w, reproj_thresh
     dev = f.device
     _chk(n, torch.int32); _chk(f, torch.float64); _chk(level, torch.int32); _chk(pos, torch.float64)
     _chk(has_point, torch.uint8); _chk(T_f_w, torch.float64)
-    if out is not None:  # reuse a result block: pose and flags are in/out for the kernel
+    c = capi.camera(cam)
+    if out is not None and not (ordered or deferred):
+        # reuse a result block: the kernel reads the pose and the flags where they are and writes the block (no copies)
+        _chk(out.has_point, torch.uint8); _chk(out.T_f_w, torch.float64)
+        assert out.has_point.numel() == has_point.numel() == B * ns and out.T_f_w.numel() == T_f_w.numel() == 12 * B
+        capi.check(lib.svo_hip_pose_optimize_into(C.byref(c), B, n.data_ptr(), ns, f.data_ptr(), level.data_ptr(), pos.data_ptr(),
+                                                  has_point.data_ptr(), T_f_w.data_ptr(), reproj_thresh, n_iter,
+                                                  out.has_point.data_ptr(), out.T_f_w.data_ptr(), out.Cov.data_ptr(),
+                                                  out.stats.data_ptr(), out.ran.data_ptr(), _stream_ptr(dev)),
+                   "svo_hip_pose_optimize_into")
+        return out
+    if out is not None:  # the in-place entries on a reused result block: pose and flags are in/out for the kernel
         res = out
         res.T_f_w.copy_(T_f_w)
         res.has_point.copy_(has_point)
@@ -264,7 +275,6 @@ def optimize_gauss_newton(cam, n, f, level, pos, has_point, T_f_w, reproj_thresh
         res = PoseOptResult(T_f_w.clone(), torch.zeros(B, 36, dtype=torch.float64, device=dev),
                             torch.zeros(B, 4, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.int32, device=dev),
                             has_point.clone())
-    c = capi.camera(cam)
     # deferred: svo_hip_pose_optimize_deferred -- frames the wave kernel hands over come back untouched with ran == 2
     fn = lib.svo_hip_pose_optimize_ordered if ordered else (lib.svo_hip_pose_optimize_deferred if deferred else lib.svo_hip_pose_optimize)
     capi.check(fn(C.byref(c), B, n.data_ptr(), ns, f.data_ptr(), level.data_ptr(), pos.data_ptr(),
