@@ -572,8 +572,14 @@ int svo_hip_frame_pose_compose(const double* d_T_cur_ref, const double* d_q_ref,
  *   d_T_f_w [B][12]        in/out Frame::T_f_w_
  *   d_Cov [B][36]          Frame::Cov_ (may be NULL)
  *   d_stats [B][4]         estimated_scale, error_init, error_final, (double)num_obs
- *   d_ran [B]              0 where no observation had a point (:57-58: nothing is touched)
+ *   d_ran [B]              SVO_HIP_POSE_RAN_NONE (0) where no observation had a point (:57-58: nothing is
+ *                          touched), SVO_HIP_POSE_RAN_DONE (1) where the frame was refined,
+ *                          SVO_HIP_POSE_RAN_ORDERED (2) where svo_hip_pose_optimize_deferred left the frame to
+ *                          svo_hip_pose_optimize_ordered (below; no other entry returns it)
  */
+#define SVO_HIP_POSE_RAN_NONE 0    /* no observation had a point: pose, flags, Cov and stats untouched */
+#define SVO_HIP_POSE_RAN_DONE 1    /* refined: every output is the frame's                              */
+#define SVO_HIP_POSE_RAN_ORDERED 2 /* left to the ordered kernel, untouched (the deferred entry only)   */
 int svo_hip_pose_optimize(const svo_hip_camera* cam, int B, const int32_t* d_n, int n_stride,
                           const double* d_f, const int32_t* d_level, const double* d_pos,
                           uint8_t* d_has_point, double reproj_thresh, int n_iter,
@@ -586,7 +592,7 @@ int svo_hip_pose_optimize_ordered(const svo_hip_camera* cam, int B, const int32_
                                   void* stream);
 
 /* svo_hip_pose_optimize without its second launch: frames the wave kernel cannot take (normal equations
- * singular to working precision, n_iter == 0) are left UNTOUCHED and reported with d_ran[b] == 2; the caller
+ * singular to working precision, n_iter == 0) are left UNTOUCHED and reported with d_ran[b] == SVO_HIP_POSE_RAN_ORDERED; the caller
  * finishes them with svo_hip_pose_optimize_ordered after looking at d_ran.  For single-stream hosts that
  * synchronise after the call anyway (the drop-in): the fix-up launch of svo_hip_pose_optimize is 5 us of an
  * otherwise 20 us call and almost never has work. */

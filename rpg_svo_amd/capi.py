@@ -176,6 +176,7 @@ HOMOGRAPHY_MAX_PTS, HOMOGRAPHY_MAX_HYPOTHESES = 1024, 4096
 REPROJ_MAX_IN_FRAME, REPROJ_MAX_CELLS, REPROJ_HEADER = 4096, 2048, 8
 FTR_CORNER, FTR_EDGELET = 0, 1
 SEED_ERASED_OLD, SEED_BEHIND, SEED_NOT_IN_FRAME, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = range(1, 8)
+POSE_RAN_NONE, POSE_RAN_DONE, POSE_RAN_ORDERED = 0, 1, 2  # SVO_HIP_POSE_RAN_*: d_ran of the svo_hip_pose_optimize entries
 
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 _LP = C.POINTER(PyrLayout)

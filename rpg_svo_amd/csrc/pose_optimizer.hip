@@ -14,14 +14,16 @@
 // and SE3::exp(dT)*T; medians are found by exact rank counting in LDS (nth_element's value).
 //
 // Entry points: svo_hip_pose_optimize, _deferred and _ordered (in place) and svo_hip_pose_optimize_into (inputs read where they
-// are) are one-line calls of pose_optimize_impl with a mode; it checks the arguments, fills one svo_track::PoseWaveArgs and hands
-// it to the wave kernel (pose_optimizer_wave.hip) and / or to launch_ordered, which builds this file's PoseArgs from it.
+// are) are one-line calls of pose_optimize_impl with a mode; it checks the arguments, fills one svo_track::PoseArgs and hands
+// it to the wave kernel (pose_optimizer_wave.hip) and / or to launch_ordered, whose kernels take the same block.  What the
+// two kernels share -- the block, the row limits, the Tukey weight, the codes of `ran`, the result lines -- is in pose_common.h.
 #pragma clang fp contract(off)
-#include "track_kernels.h"
+#include "pose_common.h"
 #include "track_math.h"
 
 using namespace svo_capi;
 using namespace svo_dev;
+using namespace svo_track;
 
 namespace {
 
@@ -29,25 +31,6 @@ constexpr int PO_MINW = 4;
 constexpr int PO_HALF = 32;
 constexpr int PO_BLOCK = 64;  // one wave per frame: the serial parts dominate, occupancy comes from many small workgroups
 static_assert(PO_BLOCK == 64, "pose_opt_flagged_kernel finds its frames with one ballot over the workgroup");
-constexpr int PO_MAXN = 1024;
-constexpr double SVO_EPS = 0.0000000001;  // svo/include/svo/global.h:77
-
-struct PoseArgs {
-  Cam cam;
-  const int32_t* n;
-  int n_stride;
-  const double* f;
-  const int32_t* level;
-  const double* pos;
-  uint8_t* has_point;
-  double reproj_thresh;
-  int n_iter;
-  double* T;
-  double* Cov;
-  double* stats;
-  int32_t* ran;
-  int B;  // frames (the scan of pose_opt_flagged_kernel stops there)
-};
 
 struct PoseLds {
   double tile[28][PO_HALF];  // half a chunk at a time: 7 KB instead of 14 KB per frame doubles the frames per CU
@@ -63,17 +46,6 @@ struct PoseLds {
   int n_err;
   int flag;  // 0 continue, 1 stop
 };
-
-// tukey: vk::robust_cost::TukeyWeightFunction::value
-__device__ __forceinline__ float tukey_weight(float x) {
-  const float b_square = 4.6851f * 4.6851f;
-  const float x_square = x * x;
-  if (x_square <= b_square) {
-    const float tmp = 1.0f - x_square / b_square;
-    return tmp * tmp;
-  }
-  return 0.0f;
-}
 
 // value with rank k among the entries of v[0..n) flagged in `hp` (ties broken by index):
 // what nth_element(begin, begin+k, end) leaves at position k.
@@ -93,6 +65,35 @@ __device__ __forceinline__ void rank_select(const T* v, int n, int k, T* out) {
   }
 }
 
+// e = (project2d(f) - project2d(T p)) * sqrt_inv_cov of observation g (:49-53, :76-84, :132-135) and pf = T p; returns
+// sqrt_inv_cov = 1 / 2^level
+__device__ __forceinline__ double po_residual(const PoseArgs& a, const size_t g, const Se3& T, double pf[3], double e[2]) {
+  const double p[3] = {a.pos[3 * g], a.pos[3 * g + 1], a.pos[3 * g + 2]};
+  const double fb[3] = {a.f[3 * g], a.f[3 * g + 1], a.f[3 * g + 2]};
+  double u0[2], u1[2];
+  se3_apply(T, p, pf);
+  project2d(fb, u0);
+  project2d(pf, u1);
+  const double k = 1.0 / (double)(1 << a.level[g]);
+  e[0] = (u0[0] - u1[0]) * k;
+  e[1] = (u0[1] - u1[1]) * k;
+  return k;
+}
+
+// The 21 sums of the packed upper triangle (row by row) times `scale` as the symmetric 6 x 6
+__device__ __forceinline__ void po_unpack_sym6(const double* acc, double scale, double A[36]) {
+  int q = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) {
+      const double v = acc[q] * scale;
+      A[r * 6 + c] = v;
+      A[c * 6 + r] = v;
+      ++q;
+    }
+}
+
 // per-observation arrays, sized by n_stride at launch (dynamic LDS):
 //   vals f64 [ns]: chi2_vec_init, later chi2_vec_final (+inf where there is no point)
 //   err  f32 [ns]: |e| for the MAD scale, later the pruning marks
@@ -106,8 +107,7 @@ struct PoseDyn {
 // Frame b, in place on a.T / a.has_point, by the PO_BLOCK lanes of the workgroup (all of them call it, with the same b).
 __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, PoseLds& s, const PoseDyn& d) {
   const int tid = threadIdx.x;
-  int n = a.n[b];
-  n = n < 0 ? 0 : (n > a.n_stride ? a.n_stride : n);  // contract: n <= n_stride; never index past the row
+  const int n = pose_row_n(a, a.n[b]);
   const size_t base = (size_t)b * a.n_stride;
   const double focal = fabs(a.cam.fx);
 
@@ -127,16 +127,8 @@ __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, P
     for (int i = tid; i < n; i += PO_BLOCK) {
       d.err[i] = INFINITY;
       if (!d.hp[i]) continue;
-      const double p[3] = {a.pos[3 * (base + i)], a.pos[3 * (base + i) + 1], a.pos[3 * (base + i) + 2]};
-      const double fb[3] = {a.f[3 * (base + i)], a.f[3 * (base + i) + 1], a.f[3 * (base + i) + 2]};
-      double pf[3], u0[2], u1[2];
-      se3_apply(T, p, pf);
-      project2d(fb, u0);
-      project2d(pf, u1);
-      double e[2] = {u0[0] - u1[0], u0[1] - u1[1]};
-      const double k = 1.0 / (double)(1 << a.level[base + i]);
-      e[0] *= k;
-      e[1] *= k;
+      double pf[3], e[2];
+      po_residual(a, base + i, T, pf, e);
       d.err[i] = (float)norm2(e);
       ++cnt;
     }
@@ -145,12 +137,12 @@ __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, P
   __syncthreads();
   const int n_err = s.n_err;
   if (n_err == 0) {  // errors.empty(): return before touching anything (:57-58)
-    if (tid == 0) a.ran[b] = 0;
+    if (tid == 0) a.ran[b] = POSE_RAN_NONE;
     return;
   }
   rank_select<float>(d.err, n, n_err / 2, &s.median_f);
   __syncthreads();
-  const double estimated_scale = (double)(1.48f * s.median_f);  // MADScaleEstimator::compute
+  const double estimated_scale = (double)(POSE_MAD_NORMALISER * s.median_f);  // MADScaleEstimator::compute
   if (tid == 0) s.scale = estimated_scale;
 
   if (tid < 28) s.acc[tid] = 0.0;
@@ -171,22 +163,14 @@ __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, P
       bool live = false;
       if (i < n && d.hp[i]) {
         live = true;
-        const double p[3] = {a.pos[3 * (base + i)], a.pos[3 * (base + i) + 1], a.pos[3 * (base + i) + 2]};
-        const double fb[3] = {a.f[3 * (base + i)], a.f[3 * (base + i) + 1], a.f[3 * (base + i) + 2]};
-        double J[12], xyz_f[3], u0[2], u1[2];
-        se3_apply(T, p, xyz_f);
+        double J[12], xyz_f[3], e[2];
+        const double sqrt_inv_cov = po_residual(a, base + i, T, xyz_f, e);
         frame_jacobian_xyz2uv(xyz_f, J);
-        project2d(fb, u0);
-        project2d(xyz_f, u1);
-        double e[2] = {u0[0] - u1[0], u0[1] - u1[1]};
-        const double sqrt_inv_cov = 1.0 / (double)(1 << a.level[base + i]);
-        e[0] *= sqrt_inv_cov;
-        e[1] *= sqrt_inv_cov;
         const double e2 = e[0] * e[0] + e[1] * e[1];
         if (iter == 0) d.vals[i] = e2;  // chi2_vec_init
 #pragma unroll
         for (int k = 0; k < 12; ++k) J[k] *= sqrt_inv_cov;
-        const double weight = (double)tukey_weight((float)(norm2(e) / scale));
+        const double weight = (double)pose_tukey_weight((float)(norm2(e) / scale));
         int q = 0;
 #pragma unroll
         for (int r = 0; r < 6; ++r)
@@ -246,13 +230,7 @@ __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, P
     }
     if (tid == 0) {
       double A[36], bv[6], dT[6];
-      int q = 0;
-      for (int r = 0; r < 6; ++r)
-        for (int c = r; c < 6; ++c) {
-          A[r * 6 + c] = s.acc[q];
-          A[c * 6 + r] = s.acc[q];
-          ++q;
-        }
+      po_unpack_sym6(s.acc, 1.0, A);
       for (int r = 0; r < 6; ++r) bv[r] = s.acc[21 + r];
       const double new_chi2 = s.acc[27];
       ldlt_solve_pivoted<6>(A, bv, dT);
@@ -297,19 +275,7 @@ __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, P
   // solves run side by side (every lane factors the same matrix: same instructions, same bits)
   if (a.Cov) {
     double Af[36];
-    {
-      const double f2 = focal * focal;  // std::pow(f, 2)
-      int q = 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = r; c < 6; ++c) {
-          const double v = s.acc[q] * f2;
-          Af[r * 6 + c] = v;
-          Af[c * 6 + r] = v;
-          ++q;
-        }
-    }
+    po_unpack_sym6(s.acc, focal * focal, Af);  // std::pow(f, 2)
     LdltReg<6> fac;
     fac.factor(Af);
     double e[6], x[6];
@@ -338,16 +304,8 @@ __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, P
       d.err[i] = 0.f;
       d.vals[i] = INFINITY;
       if (!d.hp[i]) continue;
-      const double p[3] = {a.pos[3 * (base + i)], a.pos[3 * (base + i) + 1], a.pos[3 * (base + i) + 2]};
-      const double fb[3] = {a.f[3 * (base + i)], a.f[3 * (base + i) + 1], a.f[3 * (base + i) + 2]};
-      double pf[3], u0[2], u1[2];
-      se3_apply(T, p, pf);
-      project2d(fb, u0);
-      project2d(pf, u1);
-      double e[2] = {u0[0] - u1[0], u0[1] - u1[1]};
-      const double k = 1.0 / (double)(1 << a.level[base + i]);
-      e[0] *= k;
-      e[1] *= k;
+      double pf[3], e[2];
+      po_residual(a, base + i, T, pf, e);
       d.vals[i] = e[0] * e[0] + e[1] * e[1];  // chi2_vec_final
       d.err[i] = 1.f;                         // member of chi2_vec_final
       if (norm2(e) > reproj_thresh_scaled) {
@@ -363,17 +321,11 @@ __device__ __forceinline__ void pose_opt_frame(const PoseArgs& a, const int b, P
   const int n_deleted = s.n_err;
   for (int i = tid; i < n; i += PO_BLOCK)
     if (d.err[i] == 2.f) a.has_point[base + i] = 0;  // (*it)->point = NULL
-  if (tid == 0) {
-    a.stats[4 * b + 0] = estimated_scale * focal;
-    a.stats[4 * b + 1] = a.n_iter > 0 ? sqrt(med_init) * focal : 0.0;  // chi2_vec_init empty without an iteration
-    a.stats[4 * b + 2] = sqrt(s.median_d) * focal;
-    a.stats[4 * b + 3] = (double)(n_err - n_deleted);
-    a.ran[b] = 1;
-  }
+  if (tid == 0) pose_write_result(a, b, focal, estimated_scale, med_init, s.median_d, n_err, n_deleted);
 }
 
 __device__ __forceinline__ PoseDyn pose_dyn(double* po_dyn, int n_stride) {
-  const int ns8 = (n_stride + 7) & ~7;
+  const int ns8 = pose_cap(n_stride);
   PoseDyn d;
   d.vals = po_dyn;
   d.err = reinterpret_cast<float*>(po_dyn + ns8);
@@ -388,7 +340,7 @@ __global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_kernel(const PoseA
   pose_opt_frame(a, blockIdx.x, s, pose_dyn(po_dyn, a.n_stride));
 }
 
-// The frames the wave kernel handed over (ran[b] == 2) alone: one workgroup per PO_BLOCK frames reads their PO_BLOCK words of
+// The frames the wave kernel handed over (ran[b] == POSE_RAN_ORDERED) alone: one workgroup per PO_BLOCK frames reads their PO_BLOCK words of
 // `ran` at once and runs the flagged ones one after the other, in ascending order.  Frames do not depend on each other, so
 // a frame's result is what a workgroup of its own gives; a batch without a flagged frame -- the usual one -- costs B / 64
 // workgroups of one load each instead of B.
@@ -398,7 +350,7 @@ __global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_flagged_kernel(con
   const PoseDyn d = pose_dyn(po_dyn, a.n_stride);
   const int b0 = blockIdx.x * PO_BLOCK;
   const int mine = b0 + (int)threadIdx.x;
-  unsigned long long todo = __ballot(mine < a.B && a.ran[mine] == 2);  // (read before any frame of this chunk writes its word)
+  unsigned long long todo = __ballot(mine < a.B && a.ran[mine] == POSE_RAN_ORDERED);  // (read before any frame of this chunk writes its word)
   while (todo) {
     const int k = __ffsll((long long)todo) - 1;
     todo &= todo - 1;
@@ -409,29 +361,14 @@ __global__ void __launch_bounds__(PO_BLOCK, PO_MINW) pose_opt_flagged_kernel(con
 
 }  // namespace
 
-// The ordered kernel on the frames of `w`; only_flagged = 1: on those the wave kernel handed over (ran = 2) alone.
-static int launch_ordered(const svo_track::PoseWaveArgs& w, int only_flagged, hipStream_t s) {
-  PoseArgs a;
-  a.cam = make_cam(&w.cam);
-  a.n = w.n;
-  a.n_stride = w.n_stride;
-  a.f = w.f;
-  a.level = w.level;
-  a.pos = w.pos;
-  a.has_point = w.has_point;
-  a.reproj_thresh = w.reproj_thresh;
-  a.n_iter = w.n_iter;
-  a.T = w.T;
-  a.Cov = w.Cov;
-  a.stats = w.stats;
-  a.ran = w.ran;
-  a.B = w.B;
-  const int ns8 = (w.n_stride + 7) & ~7;
-  const size_t dyn = (size_t)ns8 * (sizeof(double) + sizeof(float) + 1);
+// The ordered kernel on the frames of `a`, in place on a.has_point / a.T; only_flagged = 1: on those the wave kernel handed
+// over (ran = POSE_RAN_ORDERED) alone.
+static int launch_ordered(const PoseArgs& a, int only_flagged, hipStream_t s) {
+  const size_t dyn = (size_t)pose_cap(a.n_stride) * (sizeof(double) + sizeof(float) + 1);
   if (only_flagged)
-    hipLaunchKernelGGL(pose_opt_flagged_kernel, dim3((w.B + PO_BLOCK - 1) / PO_BLOCK), dim3(PO_BLOCK), dyn, s, a);
+    hipLaunchKernelGGL(pose_opt_flagged_kernel, dim3((a.B + PO_BLOCK - 1) / PO_BLOCK), dim3(PO_BLOCK), dyn, s, a);
   else
-    hipLaunchKernelGGL(pose_opt_kernel, dim3(w.B), dim3(PO_BLOCK), dyn, s, a);
+    hipLaunchKernelGGL(pose_opt_kernel, dim3(a.B), dim3(PO_BLOCK), dyn, s, a);
   return check_launch();
 }
 
@@ -451,7 +388,7 @@ static int pose_optimize_impl(PoseMode mode, const svo_hip_camera* cam, int B, c
   if (B == 0) return SVO_HIP_OK;
   if (!d_n || !d_f || !d_level || !d_pos || !d_has_point_in || !d_has_point || !d_T_in || !d_T_f_w || !d_stats || !d_ran)
     return SVO_HIP_EINVAL;
-  svo_track::PoseWaveArgs w;
+  PoseArgs w;
   w.cam = *cam;
   w.B = B;
   w.n = d_n;
@@ -469,16 +406,16 @@ static int pose_optimize_impl(PoseMode mode, const svo_hip_camera* cam, int B, c
   w.stats = d_stats;
   w.ran = d_ran;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == POSE_ORDERED || n_stride > svo_track::POSE_WAVE_MAX_STRIDE) {  // (more than 4 trips of 64 observations: ordered kernel)
+  if (mode == POSE_ORDERED || n_stride > POSE_WAVE_MAX_STRIDE) {  // (more than 4 trips of 64 observations: ordered kernel)
     // the ordered kernel works in place: rows this wide are the one case in which the inputs are copied first
     if (d_has_point_in != d_has_point)
       SVO_HIP_TRY(hipMemcpyAsync(d_has_point, d_has_point_in, (size_t)B * n_stride, hipMemcpyDeviceToDevice, s));
     if (d_T_in != d_T_f_w) SVO_HIP_TRY(hipMemcpyAsync(d_T_f_w, d_T_in, (size_t)B * 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
     return launch_ordered(w, 0, s);
   }
-  const int rc = svo_track::launch_pose_wave(w, s);
+  const int rc = launch_pose_wave(w, s);
   if (rc != SVO_HIP_OK || mode == POSE_WAVE_DEFERRED) return rc;
-  // frames whose normal equations are (nearly) singular were handed over with ran = 2, their flags and pose as they came in:
+  // frames whose normal equations are (nearly) singular were handed over with ran = POSE_RAN_ORDERED, their flags and pose as they came in:
   // the ordered kernel finishes exactly those, in place on the outputs (one workgroup looks at 64 frames)
   return launch_ordered(w, 1, s);
 }

@@ -34,7 +34,9 @@
 //   * MAD scale and the two reported medians are exact order statistics found by a bitwise
 //     radix select over the wave (ballot + popcount per bit), not by O(n^2) rank counting; its keys (up to four per lane)
 //     stay in registers.
-#include "track_kernels.h"
+// The argument block, the row limits, the Tukey weight, the codes of `ran` and the result lines are the ordered kernel's too:
+// pose_common.h.
+#include "pose_common.h"
 #include "track_math.h"
 #include "wave_reduce.h"
 
@@ -43,7 +45,7 @@ using namespace svo_dev;
 
 namespace {
 
-using svo_track::PoseWaveArgs;
+using namespace svo_track;
 
 // Frames (= waves) per workgroup: ONE.  Nothing ties the waves of a workgroup together but the LDS, which the hardware hands
 // out per workgroup and takes back only when its LAST wave ends: with four frames per workgroup a frame that rolled back after
@@ -52,10 +54,8 @@ using svo_track::PoseWaveArgs;
 // the byte count of the launch follow this one number; 2 and 4 were the other two builds of
 // profiles/r08a_k4_one_frame_per_workgroup.txt (compose + K4 0.2170 ms at 4, 0.2079 at 2, 0.2002 at 1; the same bytes out).
 constexpr int PW_WAVES = 1;
-constexpr int PW_TRIPS = svo_track::POSE_WAVE_MAX_STRIDE / 64;  // trips of 64 slots a row can have
+constexpr int PW_TRIPS = POSE_WAVE_MAX_STRIDE / 64;  // trips of 64 slots a row can have
 constexpr int PW_MINW = 4;  // waves per SIMD asked of the register allocator (<= 128 VGPRs)
-constexpr double SVO_EPS = 0.0000000001;  // svo/include/svo/global.h:77
-
 
 // The pose (R, t, quaternion, rollback copy) is 38 doubles: kept in VGPRs it would cost 76 registers per lane next to
 // the resident observations; uniform_f64 (device_math.h) moves them to SGPRs.
@@ -174,14 +174,6 @@ __device__ __forceinline__ Se3 se3_compose_fast(const Se3& a, const Se3& b) {
   return r;
 }
 
-// vk::robust_cost::TukeyWeightFunction::value
-__device__ __forceinline__ float tukey_w(float x) {
-  const float b_square = 4.6851f * 4.6851f;
-  const float x_square = x * x;
-  const float tmp = 1.0f - x_square / b_square;
-  return (x_square <= b_square) ? tmp * tmp : 0.0f;
-}
-
 // Exact order statistic: the value of rank k (0-based) among the wave's NPL*64 keys.  Keys are
 // bit patterns of non-negative floats/doubles (order-isomorphic to unsigned integers);
 // non-participants hold +inf.  One ballot + popcount per key and bit; the walk down the bits ends as
@@ -266,21 +258,29 @@ struct PwBlock {
   }
 };
 constexpr int PW_BYTES_PER_OBS = 5 * 8 + 4 + 1;
-__host__ __device__ constexpr int pw_cap(int n_stride) { return (n_stride + 7) & ~7; }
 
-// e = (u - project2d(T p)) * sqrt_inv_cov of one observation: e2 = |e|^2 (the residual of the two median passes; the
-// Gauss-Newton loop forms the same expressions and keeps the intermediates)
-__device__ __forceinline__ double pw_e2(const PwObs& o, const double R[9], const double t[3]) {
+// e = (u - project2d(T p)) * sqrt_inv_cov of one observation, e2 = |e|^2, and what the Jacobian is formed from: 1/z and the
+// normalised coordinates of T p.  The two median passes read e2, the Gauss-Newton loop everything: the same residuals.
+struct PwRes {
+  double zi, xn, yn, e0, e1, e2;
+};
+__device__ __forceinline__ PwRes pw_residual(const PwObs& o, const double R[9], const double t[3]) {
   const double x = R[0] * o.px + R[1] * o.py + R[2] * o.pz + t[0];
   const double y = R[3] * o.px + R[4] * o.py + R[5] * o.pz + t[1];
   const double z = R[6] * o.px + R[7] * o.py + R[8] * o.pz + t[2];
-  const double zi = fast_rcp(z);  // (as in the iterations: the same residuals as iteration 0)
-  const double e0 = (o.ux - x * zi) * o.k, e1 = (o.uy - y * zi) * o.k;
-  return e0 * e0 + e1 * e1;
+  PwRes r;
+  r.zi = fast_rcp(z);
+  r.xn = x * r.zi;
+  r.yn = y * r.zi;
+  r.e0 = (o.ux - r.xn) * o.k;  // e *= sqrt_inv_cov
+  r.e1 = (o.uy - r.yn) * o.k;
+  r.e2 = r.e0 * r.e0 + r.e1 * r.e1;
+  return r;
 }
 
-// rank k among the keys of the first `trips` (wave-uniform, 1..4) of kd[4]
-__device__ __forceinline__ double pw_select(const unsigned long long kd[4], int trips, int k) {
+// rank k among the keys of the first `trips` (wave-uniform, 1..PW_TRIPS) of kd
+__device__ __forceinline__ double pw_select(const unsigned long long kd[PW_TRIPS], int trips, int k) {
+  static_assert(PW_TRIPS == 4, "the chain below names every number of trips");
   unsigned long long r;
   if (trips <= 1) r = radix_select<1, unsigned long long>(kd, k, 62);
   else if (trips == 2) r = radix_select<2, unsigned long long>(kd, k, 62);
@@ -304,20 +304,19 @@ __device__ __forceinline__ void pw_loads_done() {
 //   6,7,9  A(1,2) A(1,3) A(1,5)          (5 and 8 stay zero)
 //   10..19 A(2,2) A(2,3) A(2,4) A(2,5) A(3,3) A(3,4) A(3,5) A(4,4) A(4,5) A(5,5)
 //   20..25 b[0..5]   26 chi2
-__global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(const PoseWaveArgs a) {
+__global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(const PoseArgs a) {
   SVO_DYNAMIC_LDS(double, pw_dyn);
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * PW_WAVES + wave);  // (the wave's: addresses off it stay in SGPRs)
   if (b >= a.B) return;
-  int n = __builtin_amdgcn_readfirstlane(a.n[b]);
-  n = n < 0 ? 0 : (n > a.n_stride ? a.n_stride : n);  // contract: n <= n_stride (svo_hip.h); never read past the row
+  const int n = pose_row_n(a, __builtin_amdgcn_readfirstlane(a.n[b]));
   const size_t base = (size_t)b * a.n_stride;
   const double focal = fabs(a.cam.fx);
 
   // ---- this wave's observations: the live ones, in index order, side by side in LDS for the whole call -----------
   PwBlock blk;
-  blk.cap = pw_cap(a.n_stride);
+  blk.cap = pose_cap(a.n_stride);
   blk.d = pw_dyn + (size_t)wave * (blk.cap / 8) * PW_BYTES_PER_OBS;  // (cap * 45 bytes per wave: a multiple of 8)
   blk.k = reinterpret_cast<float*>(blk.d + 5 * blk.cap);
   blk.slot = reinterpret_cast<uint8_t*>(blk.k + blk.cap);
@@ -385,7 +384,7 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     }
   }
   if (n_live == 0) {  // errors.empty(): return before touching anything (:57-58)
-    if (lane == 0) a.ran[b] = 0;
+    if (lane == 0) a.ran[b] = POSE_RAN_NONE;
     return;
   }
   SVO_WAVE_LDS_FENCE();  // the block is this wave's alone: its DS operations execute in order, no barrier
@@ -410,15 +409,18 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   for (int k = 0; k < 9; ++k) R[k] = uniform_f64(R[k]);
 
   // ---- error scale (:45-60) and the median of chi2_vec_init (same residuals as iteration 0) ----
+  // (This key loop and the one of the pruning pass below stay written out: as one function over the block, with the pruning
+  // tail as a callable or handing e2 and `live` back per trip, the compiler commuted the operands of four v_fma_f64 of the
+  // residual -- the same values, not the same instruction sequence; profiles/r13a_*.)
   double estimated_scale, med_init;
   {
-    unsigned long long kd[4];
+    unsigned long long kd[PW_TRIPS];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < PW_TRIPS; ++j) {
       kd[j] = 0x7ff0000000000000ull;
       if (j < trips) {
         const int at = j * 64 + lane;
-        const double e2 = pw_e2(blk.load(at < last_pos ? at : last_pos), R, T.t);
+        const double e2 = pw_residual(blk.load(at < last_pos ? at : last_pos), R, T.t).e2;
         if (at < n_live) kd[j] = (unsigned long long)__double_as_longlong(e2);
       }
     }
@@ -427,14 +429,14 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     // sqrt and the conversion are monotone, so the rank-k error IS the image of the rank-k e2 -- one selection, not two
     // (equal images of different e2 are the same value).
     const float median_f = (float)sqrt(med_init);
-    estimated_scale = (double)(1.48f * median_f);  // MADScaleEstimator::compute
+    estimated_scale = (double)(POSE_MAD_NORMALISER * median_f);  // MADScaleEstimator::compute
   }
 
   // ---- Gauss-Newton (:66-121) ----------------------------------------------------------
   double scale = estimated_scale;
   double chi2 = 0.0;
   if (a.n_iter == 0) {  // Cov_ of a never-formed A: the ordered kernel reproduces what the reference leaves behind
-    if (lane == 0) a.ran[b] = 2;
+    if (lane == 0) a.ran[b] = POSE_RAN_ORDERED;
     return;
   }
   for (int iter = 0; iter < a.n_iter; ++iter) {
@@ -448,15 +450,9 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     for (int j = 0; j < trips; ++j) {  // a lane adds its observations in trip order
       const int at = j * 64 + lane;
       const PwObs o = blk.load(at < last_pos ? at : last_pos);
-      const double x = R[0] * o.px + R[1] * o.py + R[2] * o.pz + T.t[0];
-      const double y = R[3] * o.px + R[4] * o.py + R[5] * o.pz + T.t[1];
-      const double z = R[6] * o.px + R[7] * o.py + R[8] * o.pz + T.t[2];
-      const double zi = fast_rcp(z);
-      const double xn = x * zi, yn = y * zi;
-      const double k = o.k;
-      const double e0 = (o.ux - xn) * k, e1 = (o.uy - yn) * k;  // e *= sqrt_inv_cov
-      const double e2 = e0 * e0 + e1 * e1;
-      const float wf = tukey_w((float)(fast_sqrt(e2) * inv_scale));
+      const PwRes r = pw_residual(o, R, T.t);
+      const double zi = r.zi, xn = r.xn, yn = r.yn, k = o.k, e0 = r.e0, e1 = r.e1, e2 = r.e2;
+      const float wf = pose_tukey_weight((float)(fast_sqrt(e2) * inv_scale));
       const double w = at < n_live ? (double)wf : 0.0;
       // Frame::jacobian_xyz2uv (frame.h:116-138), rows J0 / J1 scaled by sqrt_inv_cov; j11 == j00, j14 == -j03
       const double j00 = -zi * k, j02 = xn * zi * k, j03 = xn * yn * k, j04 = -(1.0 + xn * xn) * k, j05 = yn * k;
@@ -508,12 +504,12 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     // collapsed pivot means a (nearly) rank-deficient system -- fewer observations than degrees
     // of freedom -- where the reference's answer is decided by the rounding of its own ordered
     // sums inside Eigen's pivoted algorithm: such a frame is handed to the ordered kernel
-    // untouched (ran = 2; the outputs hold the frame's flags and pose as they came in and nothing else has been written).
+    // untouched (ran = POSE_RAN_ORDERED; the outputs hold the frame's flags and pose as they came in and nothing else has been written).
     double dT[6];
     double LD[21];
     ldlt6_factor_fast(A, LD);
     if (!pivots_ok(A, LD)) {
-      if (lane == 0) a.ran[b] = 2;
+      if (lane == 0) a.ran[b] = POSE_RAN_ORDERED;
       return;
     }
     ldlt6_solve(LD, bv, dT);
@@ -564,14 +560,14 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
   int n_deleted = 0;
   double med_final;
   {
-    unsigned long long kd[4];
+    unsigned long long kd[PW_TRIPS];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < PW_TRIPS; ++j) {
       kd[j] = 0x7ff0000000000000ull;
       if (j < trips) {
         const int at = j * 64 + lane;
         const int c = at < last_pos ? at : last_pos;
-        const double e2 = pw_e2(blk.load(c), R, T.t);
+        const double e2 = pw_residual(blk.load(c), R, T.t).e2;
         const bool live = at < n_live;
         if (live) kd[j] = (unsigned long long)__double_as_longlong(e2);
         // e.norm() > reproj_thresh_scaled (:136) as e2 > thresh^2: the pose this kernel arrives at differs from the reference's
@@ -586,23 +582,18 @@ __global__ void __launch_bounds__(64 * PW_WAVES, PW_MINW) pose_opt_wave_kernel(c
     }
     med_final = pw_select(kd, trips, n_live / 2);
   }
-  if (lane == 0) {
-    a.stats[4 * b + 0] = estimated_scale * focal;
-    a.stats[4 * b + 1] = a.n_iter > 0 ? sqrt(med_init) * focal : 0.0;  // chi2_vec_init is empty without an iteration
-    a.stats[4 * b + 2] = sqrt(med_final) * focal;
-    a.stats[4 * b + 3] = (double)(n_live - n_deleted);
-    a.ran[b] = 1;
-  }
+  if (lane == 0) pose_write_result(a, b, focal, estimated_scale, med_init, med_final, n_live, n_deleted);
 }
 
 }  // namespace
 
 namespace svo_track {
 
-// n_stride <= 256 only (the radix select keeps 4 keys per lane in registers); the caller falls back to the ordered kernel beyond
-int launch_pose_wave(const PoseWaveArgs& a, hipStream_t s) {
+// n_stride <= POSE_WAVE_MAX_STRIDE only (the radix select keeps PW_TRIPS keys per lane in registers); the caller falls back to
+// the ordered kernel beyond
+int launch_pose_wave(const PoseArgs& a, hipStream_t s) {
   const int grid = (a.B + PW_WAVES - 1) / PW_WAVES;
-  const size_t lds = (size_t)PW_WAVES * pw_cap(a.n_stride) * PW_BYTES_PER_OBS;  // <= PW_WAVES * 11 520 bytes
+  const size_t lds = (size_t)PW_WAVES * pose_cap(a.n_stride) * PW_BYTES_PER_OBS;  // <= PW_WAVES * 11 520 bytes
   hipLaunchKernelGGL(pose_opt_wave_kernel, dim3(grid), dim3(64 * PW_WAVES), lds, s, a);
   return check_launch();
 }

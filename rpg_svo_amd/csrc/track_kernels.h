@@ -1,4 +1,5 @@
-// track_kernels.h -- internal launchers shared by the matcher / depth-filter entry points.
+// track_kernels.h -- internal launchers shared by the matcher / depth-filter entry points (K2, K3) and the workspace carver
+// (K4's argument block and launcher: pose_common.h).
 #pragma once
 #include "capi_common.h"
 
@@ -62,28 +63,6 @@ struct WarpArgs {
   const int32_t* M_dev = nullptr;  // see AlignArgs::M_dev
 };
 int launch_warp(const WarpArgs& a, hipStream_t s);
-
-// K4 (pose_optimizer_wave.hip): one wave per frame, n_stride <= 256 (dynamic LDS: 45 bytes per slot and wave)
-struct PoseWaveArgs {
-  svo_hip_camera cam;
-  int B;
-  const int32_t* n;
-  int n_stride;
-  const double* f;
-  const int32_t* level;
-  const double* pos;
-  const uint8_t* has_point_in;  // the flags and the pose as the caller has them; == has_point / T: in place
-  uint8_t* has_point;           // out: every byte of every row (slots >= n: as they came in)
-  double reproj_thresh;
-  int n_iter;
-  const double* T_in;
-  double* T;                    // out: written on every exit (T_in where the kernel leaves the pose alone)
-  double* Cov;
-  double* stats;
-  int32_t* ran;
-};
-constexpr int POSE_WAVE_MAX_STRIDE = 256;
-int launch_pose_wave(const PoseWaveArgs& a, hipStream_t s);
 
 // carve 256-byte aligned arrays out of a caller-provided workspace
 struct Carver {

@@ -115,13 +115,13 @@ void optimizeOnDevice(const double reproj_thresh, const size_t n_iter, const boo
       else svo_hip::check(svo_hip_stream_sync(sp.stream), "svo_hip_stream_sync");
       wait_timer.unmarshal();
       // the device applied the selection rule on its own: it must have picked the trials the host picked; a frame the
-      // wave kernel left to the ordered kernel (ran == 2: singular normal equations) takes the ordinary call below
-      agree = *sp.n_sel == (int32_t)n && *sp.ran != 2;
+      // wave kernel left to the ordered kernel (SVO_HIP_POSE_RAN_ORDERED: singular normal equations) takes the ordinary call below
+      agree = *sp.n_sel == (int32_t)n && *sp.ran != SVO_HIP_POSE_RAN_ORDERED;
       for (size_t k = 0; agree && k < n; ++k) agree = sp.sel[k] == sp.trial[k];
       dev.countSpeculation(agree);
       if (agree) {
-        if (*sp.ran) applyResult(frame, sp.T, sp.Cov, sp.stats, sp.has_point, verbose, estimated_scale, error_init, error_final, num_obs);
-        return;  // ran == 0: no observation carried a point, the reference returns untouched (:57-58)
+        if (*sp.ran != SVO_HIP_POSE_RAN_NONE) applyResult(frame, sp.T, sp.Cov, sp.stats, sp.has_point, verbose, estimated_scale, error_init, error_final, num_obs);
+        return;  // SVO_HIP_POSE_RAN_NONE: no observation carried a point, the reference returns untouched (:57-58)
       }
     }
   }
@@ -159,14 +159,14 @@ void optimizeOnDevice(const double reproj_thresh, const size_t n_iter, const boo
   const svo_hip_camera cam = cameraOf(frame->cam_);
   stage_timer.device(a.used());
   a.uploadAll(lane.stream);
-  // the wave kernel alone; a frame it hands over (ran == 2: singular normal equations, n_iter == 0) is rare
+  // the wave kernel alone; a frame it hands over (SVO_HIP_POSE_RAN_ORDERED: singular normal equations, n_iter == 0) is rare
   // and found out after the sync this call needs anyway, so the single-stream path pays for one launch
   svo_hip::check(svo_hip_pose_optimize_deferred(&cam, 1, d_n, (int)n, d_f, d_level, d_pos, d_has_out, reproj_thresh,
                                                 (int)n_iter, d_Tout, d_Cov, d_stats, d_ran, lane.stream),
                  "svo_hip_pose_optimize_deferred");
   a.download(lane.stream);
   dev.finish(lane);
-  if (*ran == 2) {  // untouched by the wave kernel: the ordered kernel on the same blocks
+  if (*ran == SVO_HIP_POSE_RAN_ORDERED) {  // untouched by the wave kernel: the ordered kernel on the same blocks
     svo_hip::check(svo_hip_pose_optimize_ordered(&cam, 1, d_n, (int)n, d_f, d_level, d_pos, d_has_out, reproj_thresh,
                                                  (int)n_iter, d_Tout, d_Cov, d_stats, d_ran, lane.stream),
                    "svo_hip_pose_optimize_ordered");
@@ -175,7 +175,7 @@ void optimizeOnDevice(const double reproj_thresh, const size_t n_iter, const boo
   }
   stage_timer.unmarshal();
 
-  if (!*ran) return;  // no observation carried a point: the reference returns untouched (:57-58)
+  if (*ran == SVO_HIP_POSE_RAN_NONE) return;  // no observation carried a point: the reference returns untouched (:57-58)
   applyResult(frame, Tout, Cov, stats, has_out, verbose, estimated_scale, error_init, error_final, num_obs);
 }
 }  // namespace

@@ -186,7 +186,7 @@ struct Prediction {
   // write them, so on the lane's stream, and the selection kernel stores `flag` when it starts, i.e. when the match
   // kernels are through: `wait` polls that instead of waiting for the stream.  Mirrored arena: behind the match results
   // on the lane's second stream, so that `wait` for the lane's stream ends with the copy of the match results.
-  // (The wave kernel alone: a frame it hands over, ran == 2, is finished by the optimizer's drop-in.)
+  // (The wave kernel alone: a frame it hands over, SVO_HIP_POSE_RAN_ORDERED, is finished by the optimizer's drop-in.)
   template <class Select>
   void enqueue(svo_hip::Arena& a, svo_hip::Lane& lane, const svo_hip_camera& cam, svo_hip::Speculation& sp, bool wait,
                Select select) const {

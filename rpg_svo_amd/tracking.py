@@ -242,7 +242,7 @@ class PoseOptResult:
     T_f_w: torch.Tensor       # [B,12]
     Cov: torch.Tensor         # [B,36]
     stats: torch.Tensor       # [B,4] estimated_scale, error_init, error_final, num_obs
-    ran: torch.Tensor         # [B] i32
+    ran: torch.Tensor         # [B] i32 capi.POSE_RAN_*
     has_point: torch.Tensor   # [B,ns] u8 after pruning
 
 
@@ -275,7 +275,8 @@ def optimize_gauss_newton(cam, n, f, level, pos, has_point, T_f_w, reproj_thresh
         res = PoseOptResult(T_f_w.clone(), torch.zeros(B, 36, dtype=torch.float64, device=dev),
                             torch.zeros(B, 4, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.int32, device=dev),
                             has_point.clone())
-    # deferred: svo_hip_pose_optimize_deferred -- frames the wave kernel hands over come back untouched with ran == 2
+    # deferred: svo_hip_pose_optimize_deferred -- frames the wave kernel hands over come back untouched with
+    # ran == capi.POSE_RAN_ORDERED
     fn = lib.svo_hip_pose_optimize_ordered if ordered else (lib.svo_hip_pose_optimize_deferred if deferred else lib.svo_hip_pose_optimize)
     capi.check(fn(C.byref(c), B, n.data_ptr(), ns, f.data_ptr(), level.data_ptr(), pos.data_ptr(),
                   res.has_point.data_ptr(), reproj_thresh, n_iter, res.T_f_w.data_ptr(),
