@@ -1154,6 +1154,109 @@ int svo_hip_frame_close(const svo_hip_camera* cam, int B, int n_stride, int kf_s
                         const svo_hip_frame_close_in* in, int cell_size, int grid_n_cols, int grid_n_rows, int cells,
                         const svo_hip_frame_close_params* params, const svo_hip_frame_close_out* out, void* stream);
 
+/* ---- K12: a resident map per sequence, and the keyframe that enters it (frame_handler_mono.cpp:193-232) ----------- */
+/*
+ * svo_hip_seq_map: the map of B sequences in caller-owned device memory, with fixed capacities kf_stride K <= 64,
+ * ftr_stride F <= 1024, pt_stride P <= 8192, obs_stride R <= 64.  Keyframes live in STORAGE SLOTS that never move; frame
+ * g = b * K + slot of the state's own frame table (d_kf_store_slot, d_kf_T: a svo_hip_frames of B * K rows) is slot `slot`
+ * of sequence b.  A point is an index p < P of its sequence; its observation records are rows (b * P + p) * R + r, r <
+ * n_obs, IN Point::obs_ LIST ORDER (a push to the front shifts the others), with the columns of svo_hip_features:
+ * d_obs_kf is d_frame (the frame g), so svo_hip_find_match_direct[_indirect] reads a point's records where they lie.
+ * d_obs_row is the Feature's row in that keyframe's table, -1 = in no fts_ (the Feature of a candidate).  Feature type and
+ * gradient are not carried (corners only), n_failed_reproj_ / n_succeeded_reproj_ neither.
+ * A feature or a key point "has a point" when its index lies in [0, P) and that point's type is not 0; a record names a
+ * feature when its kf lies in [b * K, b * K + K) and its row in [0, n_fts) of that slot (n_fts read clamped to [0, F],
+ * n_obs to [0, R], n_kf to [0, K]).  Whatever does not, is treated as NULL: no index is used before its range test.
+ * Bytes beyond a count (rows >= n_fts, records >= n_obs, the tables of a free slot) are unspecified but never written
+ * except as stated below.
+ */
+#define SVO_HIP_SEQ_MAP_MAX_KFS 64
+#define SVO_HIP_SEQ_MAP_MAX_FTS 1024
+#define SVO_HIP_SEQ_MAP_MAX_PTS 8192
+#define SVO_HIP_SEQ_MAP_MAX_OBS 64
+typedef struct svo_hip_seq_map {
+  int32_t kf_stride, ftr_stride, pt_stride, obs_stride; /* K, F, P, R                                              */
+  int32_t* d_n_kf;          /* [B] keyframes in the map                                                             */
+  int32_t* d_kf_list;       /* [B][K] storage slots in Map::keyframes_ order, -1 beyond n_kf                        */
+  int32_t* d_kf_store_slot; /* [B*K] pyramid-store slot of the keyframe (svo_hip_frames.d_slot)                     */
+  double* d_kf_T;           /* [B*K][12] Frame::T_f_w_ (svo_hip_frames.d_T_f_w)                                     */
+  int32_t* d_kf_n_fts;      /* [B*K] rows of the keyframe's table (Frame::fts_.size()); 0 in a free slot            */
+  int32_t* d_kf_key_pts;    /* [B*K][5] Frame::key_pts_ as rows of the table, -1 = NULL                             */
+  double* d_ftr_px;         /* [B*K][F][2] Feature::px, fts_ order                                                  */
+  double* d_ftr_f;          /* [B*K][F][3] Feature::f                                                               */
+  int32_t* d_ftr_level;     /* [B*K][F]                                                                             */
+  int32_t* d_ftr_point;     /* [B*K][F] Feature::point as an index of the sequence's points, -1 = NULL              */
+  double* d_pt_pos;         /* [B][P][3] Point::pos_                                                                */
+  int32_t* d_pt_type;       /* [B][P] svo_hip_map's codes: 0 deleted (no point), 1 candidate, 2 unknown, 3 good     */
+  int32_t* d_pt_order;      /* [B][P] a key ascending along MapPointCandidates::candidates_; ties: smaller index    */
+  int32_t* d_pt_n_obs;      /* [B][P] Point::obs_.size()                                                            */
+  int32_t* d_obs_kf;        /* [B][P][R] frame g of the observation                                                 */
+  int32_t* d_obs_row;       /* [B][P][R] its row in that keyframe's table, -1 = in no list                          */
+  int32_t* d_obs_level;     /* [B][P][R]                                                                            */
+  double* d_obs_px;         /* [B][P][R][2]                                                                         */
+  double* d_obs_f;          /* [B][P][R][3]                                                                         */
+} svo_hip_seq_map;
+/*
+ * svo_hip_keyframe_insert: what FrameHandlerMono::processFrame does to the map after setKeyframe() (:196-200, :224-232;
+ * Point::addFrameRef, MapPointCandidates::addCandidatePointToFrame / removeFrameCandidates, Map::safeDeleteFrame with
+ * removePtFrameRef / safeDeletePoint, Frame::removeKeyPoint / setKeyPoints, Map::addKeyframe), for B sequences in one
+ * launch, in place.  Only a sequence with d_result == SVO_HIP_RESULT_IS_KEYFRAME acts; of every other one no byte of the
+ * state changes.  The new frame is what svo_hip_frame_close saw: n = d_n clamped to [0, n_stride] rows of d_px / d_f /
+ * d_level / d_has_point (after pruning), d_ftr_point = the point behind each row, d_T_out, the frame's pyramid slot d_slot,
+ * and svo_hip_frame_close_out's d_key_pts (a value outside [0, n) is NULL) and d_kf_remove (an index into kf_list; outside
+ * [0, n_kf): nothing is removed).  cam gives width and height.  The outputs tests/keyframe_insert_checker.py's lists give:
+ *  0. The new frame takes the smallest storage slot that is not in kf_list.  A row has its point when has_point != 0 and
+ *     ftr_point names a point (above).  One point has at most one feature per frame: of several rows with the same point
+ *     the first keeps it, the others count as rows without a point.  Capacities are tested before anything is written: no
+ *     free slot, n > F, a point that would hold more than R records, an origin keyframe whose table would pass F give
+ *     status 1 and leave the state untouched; a kf_list entry outside [0, K) gives status 2 likewise.
+ *  1. The slot's T, pyramid slot, n_fts = n, key_pts and table are written (point -1 for a row without one); every row
+ *     with a point becomes that point's FRONT record (kf, row, level, px, f), the others shift back.
+ *  2. Every candidate (type 1) that got such a record, and whose LAST record is its own Feature (row -1, its kf a
+ *     keyframe of kf_list), becomes type 2; that Feature is appended to the table of its keyframe, at n_fts + its rank among
+ *     the candidates promoted into the same keyframe in (order, index) order, and the record's row becomes that row.  No
+ *     key point is tested.  A candidate whose last record is anything else stays one.
+ *  3. With a keyframe to remove (slot kf_list[kf_remove]): every row of its table, appended ones included, loses its point
+ *     (duplicates as in 0).  A point with n_obs <= 2 at that moment is deleted: in list order its records' features lose
+ *     their point and Frame::removeKeyPoint runs on their frames -- when the row is one of the frame's key points, that
+ *     slot and every slot whose feature has no point become NULL and Frame::checkKeyPoints runs over the frame's features
+ *     with a point, in row order, from the key points still standing (strictly better replaces; csrc/frame_keys.h's
+ *     keys) -- on the state of that moment: the deletions are applied one after the other in the removed frame's row
+ *     order.  Then type = 0 and n_obs = 0.  Any other point loses its first record of that keyframe (later ones move
+ *     up).  The slot ends with n_fts = 0, key_pts -1 and point -1 in every row it had, and leaves kf_list (later entries
+ *     move up).  Every remaining candidate whose last record is its own Feature in that keyframe gets type 0, n_obs 0.
+ *  4. The new slot goes to the back of kf_list; entries beyond n_kf are -1.
+ * Outputs, written for every sequence: status (0, 1, 2 above), kf_new_slot and kf_removed_slot (-1: none; the caller
+ * drops the seeds of that slot), n_promoted, n_points_deleted (the points step 3 gave type 0).  A sequence that does not
+ * act, or whose status is not 0, gets -1, -1, 0, 0.  One workgroup per sequence, integer LDS atomics only: the same
+ * call gives the same bits, and so do identical sequences wherever they stand in the batch.
+ * Limits: a null pointer (the row arrays only where n_stride > 0), a negative size or a capacity < 1: SVO_HIP_EINVAL;
+ * n_stride > 1024, a capacity beyond its maximum, B * K or B * P * R beyond 2^31 - 1: SVO_HIP_ERANGE; B == 0 is a
+ * successful no-op that touches nothing.  No input or output may alias the state.
+ */
+typedef struct svo_hip_keyframe_insert_in {
+  const int32_t* d_result;    /* [B] SVO_HIP_RESULT_*                 */
+  const int32_t* d_n;         /* [B]                                  */
+  const double* d_px;         /* [B][n_stride][2]                     */
+  const double* d_f;          /* [B][n_stride][3]                     */
+  const int32_t* d_level;     /* [B][n_stride]                        */
+  const uint8_t* d_has_point; /* [B][n_stride]                        */
+  const int32_t* d_ftr_point; /* [B][n_stride] point index per row    */
+  const double* d_T_out;      /* [B][12]                              */
+  const int32_t* d_slot;      /* [B] the frame's pyramid-store slot   */
+  const int32_t* d_key_pts;   /* [B][5] rows, -1 = NULL               */
+  const int32_t* d_kf_remove; /* [B] index into kf_list, -1 = none    */
+} svo_hip_keyframe_insert_in;
+typedef struct svo_hip_keyframe_insert_out {
+  int32_t* d_status;           /* [B] 0 ok, 1 capacity, 2 kf_list     */
+  int32_t* d_kf_new_slot;      /* [B] storage slot, -1 = none         */
+  int32_t* d_kf_removed_slot;  /* [B] storage slot, -1 = none         */
+  int32_t* d_n_promoted;       /* [B]                                 */
+  int32_t* d_n_points_deleted; /* [B]                                 */
+} svo_hip_keyframe_insert_out;
+int svo_hip_keyframe_insert(const svo_hip_camera* cam, int B, int n_stride, const svo_hip_seq_map* map,
+                            const svo_hip_keyframe_insert_in* in, const svo_hip_keyframe_insert_out* out, void* stream);
+
 /* static DepthFilter::computeTau(T_ref_cur, f, z, px_error_angle) (depth_filter.cpp:334-350) for S
  * independent measurements: d_t_ref_cur [S][3] = T_ref_cur.translation(), d_f [S][3], d_z [S].
  * Arithmetic (since round 5, here and inside svo_hip_update_seeds*): the ALGEBRAIC form -- alpha and beta enter only

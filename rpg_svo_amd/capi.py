@@ -165,6 +165,31 @@ class FrameCloseOut(C.Structure):
     _fields_ = [("d_" + n, C.c_void_p) for n in FRAME_CLOSE_OUTPUTS]
 
 
+SEQ_MAP_FIELDS = ("n_kf", "kf_list", "kf_store_slot", "kf_T", "kf_n_fts", "kf_key_pts", "ftr_px", "ftr_f", "ftr_level", "ftr_point", "pt_pos",
+                  "pt_type", "pt_order", "pt_n_obs", "obs_kf", "obs_row", "obs_level", "obs_px", "obs_f")
+
+
+class SeqMap(C.Structure):
+    """svo_hip_seq_map: the resident map of B sequences (capacities, then device pointers)."""
+    _fields_ = [(n, C.c_int32) for n in ("kf_stride", "ftr_stride", "pt_stride", "obs_stride")] + [("d_" + n, C.c_void_p) for n in SEQ_MAP_FIELDS]
+
+
+KEYFRAME_INSERT_INPUTS = ("result", "n", "px", "f", "level", "has_point", "ftr_point", "T_out", "slot", "key_pts", "kf_remove")
+KEYFRAME_INSERT_OUTPUTS = ("status", "kf_new_slot", "kf_removed_slot", "n_promoted", "n_points_deleted")
+
+
+class KeyframeInsertIn(C.Structure):
+    """svo_hip_keyframe_insert_in: inputs of svo_hip_keyframe_insert (device pointers)."""
+    _fields_ = [("d_" + n, C.c_void_p) for n in KEYFRAME_INSERT_INPUTS]
+
+
+class KeyframeInsertOut(C.Structure):
+    """svo_hip_keyframe_insert_out: outputs of svo_hip_keyframe_insert (device pointers)."""
+    _fields_ = [("d_" + n, C.c_void_p) for n in KEYFRAME_INSERT_OUTPUTS]
+
+
+SEQ_MAP_MAX_KFS, SEQ_MAP_MAX_FTS, SEQ_MAP_MAX_PTS, SEQ_MAP_MAX_OBS = 64, 1024, 8192, 64
+POINT_DELETED, POINT_CANDIDATE, POINT_UNKNOWN, POINT_GOOD = 0, 1, 2, 3
 INIT_FAILURE, INIT_NO_KEYFRAME, INIT_SUCCESS = 0, 1, 2
 TRACKING_INSUFFICIENT, TRACKING_BAD, TRACKING_GOOD = 0, 1, 2
 RESULT_NO_KEYFRAME, RESULT_IS_KEYFRAME, RESULT_FAILURE = 0, 1, 2
@@ -285,6 +310,7 @@ PROTOTYPES = {
     "svo_hip_frame_close_params_default": (_i, [C.POINTER(FrameCloseParams)]),
     "svo_hip_frame_close": (_i, [C.POINTER(Camera), _i, _i, _i, C.POINTER(FrameCloseIn), _i, _i, _i, _i, C.POINTER(FrameCloseParams),
                                  C.POINTER(FrameCloseOut), _vp]),
+    "svo_hip_keyframe_insert": (_i, [C.POINTER(Camera), _i, _i, C.POINTER(SeqMap), C.POINTER(KeyframeInsertIn), C.POINTER(KeyframeInsertOut), _vp]),
     "svo_hip_compute_tau_batch": (_i, [_i, _vp, _vp, _vp, C.c_double, _vp, _vp]),
 }
 

@@ -20,7 +20,13 @@ the shapes, against the HBM rate.
 
 --step frame_close times the end of a tracked frame (svo_hip_frame_close, csrc/frame_close.hip) on 1 and 4096 sequences x 121
 rows x 10 keyframes (max_fts + 1 features, a full keyframe list) and writes profiles/frame_close_bench.json in the same
-form: device events, the kernel's own time from a rocprofv3 run of its own, the compiler's figures and the bytes per sequence."""
+form: device events, the kernel's own time from a rocprofv3 run of its own, the compiler's figures and the bytes per sequence.
+
+--step keyframe_insert times a keyframe entering the resident map (svo_hip_keyframe_insert, csrc/keyframe_insert.hip) on 4096
+sequences of 10 keyframes x 121 features, about 1400 points and candidates, a removal and a handful of promotions each (16
+distinct maps of tests/keyframe_insert_cases.py, repeated; the state is restored before every timed call) and writes
+profiles/keyframe_insert_bench.json: device events, the kernel's own time from a rocprofv3 run, the compiler's figures and the
+bytes moved, counted from the shapes, against the HBM rate."""
 from __future__ import annotations
 
 import argparse
@@ -353,6 +359,135 @@ def main_frame_close(args):
     print(json.dumps(res))
 
 
+# ---- a keyframe enters the resident map (K12) ----------------------------------------------------------------------------
+KI_DIMS = (12, 140, 2000, 12)      # K, F, P, R: ten keyframes, the new one and a spare slot; 121 rows and the promotions
+KEYFRAME_INSERT_KERNEL = "keyframe_insert_kernel"
+
+
+def keyframe_insert_bytes(rows, with_point, mean_obs, promoted, removed_rows, deleted, P, K):
+    """bytes one sequence moves, from the shapes: the frame's rows are read once and written into the table; a row with a point
+    reads that point's type and count, moves its records one place back (52 bytes each, read and written) and writes the new
+    front record; a promotion reads and writes one record and one table row; the leaving keyframe's rows are read and nulled,
+    their points' counts read, one record list shifted (half of it on average) or, for a deleted point, two records read and
+    one table row nulled; every point's type is read once for removeFrameCandidates; the lists and key points of K slots."""
+    rec, row = 52, 48
+    frame = rows * (16 + 24 + 4 + 1 + 4) + rows * row + 96 * 2 + 5 * 4 * 2
+    refs = with_point * (8 + mean_obs * rec * 2 + rec + 4)
+    promotions = promoted * (2 * rec + row + 8)
+    walk = removed_rows * (4 + 4 + 4) + (removed_rows - deleted) * (mean_obs * rec) + deleted * (2 * 12 + 4 + 8)
+    return frame + refs + promotions + walk + 4 * P + K * (4 * 2 + 4 + 20) + 5 * 4
+
+
+def compiler_resources_keyframe_insert():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    with tempfile.TemporaryDirectory() as tmp:
+        from rpg_svo_amd.build import FLAGS
+        r = subprocess.run([hipcc, *FLAGS, "-c", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rpg_svo_amd", "csrc"),
+                            os.path.join(ROOT, "rpg_svo_amd", "csrc", "keyframe_insert.hip"), "-o", os.path.join(tmp, "ki.o"),
+                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    for blk in r.stderr.split("Function Name: ")[1:]:
+        if KEYFRAME_INSERT_KERNEL in blk.split()[0]:
+            g = lambda key: int(re.search(key + r": (\d+)", blk).group(1))
+            return {"vgprs": g("VGPRs"), "agprs": g("AGPRs"), "sgprs": g("TotalSGPRs"), "scratch_bytes_per_lane": g(r"ScratchSize \[bytes/lane\]"),
+                    "occupancy_waves_per_simd": g(r"Occupancy \[waves/SIMD\]"), "lds_bytes_per_block": g(r"LDS Size \[bytes/block\]")}
+    return "not measured"
+
+
+def time_keyframe_insert(dev, n_seq, steps, warmup):
+    """every timed call starts from the same map: the state is restored from a saved copy outside the events"""
+    import numpy as np
+    import torch
+    import first_map_cases
+    import keyframe_insert_cases as cases
+    import keyframe_insert_checker as chk
+    from rpg_svo_amd import sequence_map as sm
+    cam = first_map_cases.camera(752, 480)
+    K, F, P, R = KI_DIMS
+    distinct = min(16, n_seq)
+    seqs = [cases.random_seq(cam, KI_DIMS, ROWS, 9000 + k, KEYFRAMES, ROWS, ROWS, k % KEYFRAMES, n_cand=650, max_obs=2, n_pts=1200, match_cands=0.01)
+            for k in range(distinct)]
+    b = cases.batch("bench", cam, KI_DIMS, ROWS, seqs)
+    reps = -(-n_seq // distinct)
+    tile = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev).repeat(reps, *([1] * (v.ndim - 1)))
+    state = {k: tile(b.state[k]) for k in chk.STATE}
+    per_frame = lambda t: t[:n_seq * K].contiguous() if t.shape[0] == reps * distinct * K else t[:n_seq].contiguous()
+    state = {k: per_frame(t) for k, t in state.items()}
+    seq = torch.arange(n_seq, device=dev)
+    state["obs_kf"] += ((seq - seq % distinct) * K).to(torch.int32)[:, None, None]      # frame = b * K + slot
+    smap = sm.SequenceMap(n_seq, K, F, P, R, cam=cam, **state)
+    saved = smap.clone()
+    inp = {k: tile(b.inputs[0][k])[:n_seq].contiguous() for k in chk.INPUTS}
+    out, times = None, []
+    for i in range(warmup + steps):
+        smap.copy_(saved)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = sm.insert_keyframe(smap, inp, out=out)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            times.append(e0.elapsed_time(e1))
+    times.sort()
+    med = times[len(times) // 2]
+    want = b.expect[0][1]
+    assert all(np.array_equal(getattr(out, k)[:distinct].cpu().numpy(), want[k]) for k in chk.OUTPUTS), "the batch does not give the checker's outputs"
+    with_point = float(np.mean([(b.expect[0][0]["ftr_point"][s * K + want["kf_new_slot"][s], :ROWS] >= 0).sum() for s in range(distinct)]))
+    live = b.state["pt_type"] != 0
+    removed_rows = float(np.mean([b.state["kf_n_fts"][s * K + b.state["kf_list"][s, b.inputs[0]["kf_remove"][s]]] for s in range(distinct)]))
+    shape = dict(rows=ROWS, with_point=with_point, mean_obs=float(b.state["pt_n_obs"][live].mean()), promoted=float(want["n_promoted"].mean()),
+                 removed_rows=removed_rows, deleted=float(want["n_points_deleted"].mean()), P=P, K=K)
+    return {"sequences": n_seq, "keyframes": KEYFRAMES, "capacities_K_F_P_R": list(KI_DIMS), "points": float(live.sum(axis=1).mean()), "steps": steps,
+            "call_ms_median": med, "call_ms_min": times[0], "call_ms_max": times[-1], "sequences_per_s": n_seq / (med * 1e-3), "per_sequence": shape,
+            "status_ok_fraction": float((out.status == 0).float().mean().item()), "bytes_per_sequence": keyframe_insert_bytes(**shape)}
+
+
+def traced_keyframe_insert_ms(args):
+    """Kernel time of the replay shape from rocprofv3's kernel trace, in a run of its own."""
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    out = tempfile.mkdtemp(prefix="keyframe_insert_trace_", dir=os.path.join(ROOT, "build"))
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "trace", "--", sys.executable,
+           os.path.abspath(__file__), "--step", "keyframe_insert", "--traced-child", "--pairs", str(args.pairs)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    files = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
+    if r.returncode != 0 or not files:
+        return {"error": f"rocprofv3 exit {r.returncode}: {r.stderr[-400:]}"}
+    for row in csv.DictReader(open(files[0])):
+        if KEYFRAME_INSERT_KERNEL in row.get("Name", ""):
+            return {"calls": int(row["Calls"]), "average_ms": float(row["AverageNs"]) * 1e-6, "min_ms": float(row["MinNs"]) * 1e-6,
+                    "max_ms": float(row["MaxNs"]) * 1e-6}
+    return {"error": "the kernel is not in the trace"}
+
+
+def main_keyframe_insert(args):
+    import torch
+    out = args.out or os.path.join(ROOT, "profiles", "keyframe_insert_bench.json")
+    if not torch.cuda.is_available():
+        res = {"device": "not measured", "replay_batch": "not measured", "rocprofv3": "not measured",
+               "compiler": "not measured" if args.no_compiler else compiler_resources_keyframe_insert(),
+               "note": "no MI355X was available: nothing here is measured without one"}
+    else:
+        dev = torch.device("cuda:0")
+        if args.traced_child:
+            time_keyframe_insert(dev, args.pairs, 3, 1)
+            return
+        res = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("SVO_HIP_LIB", "in-tree")}
+        res["replay_batch"] = time_keyframe_insert(dev, args.pairs, args.steps, args.warmup)
+        res["compiler"] = "not measured" if args.no_compiler else compiler_resources_keyframe_insert()
+        res["rocprofv3"] = "not measured" if args.no_trace else traced_keyframe_insert_ms(args)
+        kern = res["rocprofv3"].get("average_ms") if isinstance(res["rocprofv3"], dict) else None
+        t_ms = kern if kern else res["replay_batch"]["call_ms_median"]
+        nbytes = res["replay_batch"]["bytes_per_sequence"] * args.pairs
+        res["hbm_bound"] = {"time_basis": "rocprofv3 kernel time" if kern else "device events", "time_ms": t_ms, "bytes": nbytes,
+                            "peak_bytes_per_s": PEAK_HBM_BYTES, "least_ms_by_bytes": nbytes / PEAK_HBM_BYTES * 1e3,
+                            "achieved_bytes_per_s": nbytes / (t_ms * 1e-3), "share_of_bound": nbytes / PEAK_HBM_BYTES * 1e3 / t_ms,
+                            "frame_close_kernel_ms_same_batch": 0.082}
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--pairs", type=int, default=4096)
@@ -361,13 +496,15 @@ def main():
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--no-compiler", action="store_true", help="skip the compile that reports registers, scratch and occupancy")
     ap.add_argument("--traced-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--step", choices=("homography", "first_map", "frame_close"), default="homography", help="which step of the bootstrap to time")
+    ap.add_argument("--step", choices=("homography", "first_map", "frame_close", "keyframe_insert"), default="homography", help="which step of the bootstrap to time")
     ap.add_argument("--out", default=None, help="default: profiles/<step>_bench.json")
     args = ap.parse_args()
     if args.step == "first_map":
         return main_first_map(args)
     if args.step == "frame_close":
         return main_frame_close(args)
+    if args.step == "keyframe_insert":
+        return main_keyframe_insert(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "homography_bench.json")
     import torch
     if not torch.cuda.is_available():
